@@ -50,18 +50,58 @@ def parse():
                     help="batch: the default sharded batch (weak scaling); fourstep: ONE transform of n = 2^log-n split over "
                          "the ranks with one all-to-all (BASELINE configs[4]; use --log-n 27, the field's limit); slab-sp: the same "
                          "transform driven from ONE process over --gpus devices through the C ABI (toyni_ntt_slab_multi_gpu_device)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="batch workload: after the timed steps write what the last step left in the batch (roundtrip.npy) and the forward "
+                         "transform of a seeded choice of its transforms (forward.npy) as float64, 48 MB at most (rank 0's shard)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "batch":
+        ap.error("--dump-outputs is implemented for the batch workload only")
+    return args
+
+
+DUMP_ELEMS = 1 << 22   # roundtrip.npy: the whole batch up to 2^22 elements, else a seeded sample of 2^22 (32 MB in float64)
+DUMP_FORWARD_ELEMS = 1 << 21   # forward.npy: whole transforms up to 2^21 elements, else a seeded sample of one transform (16 MB)
+
+
+def dump_outputs(dirname, ctx, data, batch, n, stream):
+    """--dump-outputs: `data` as the last timed step left it, and the forward half of the step (the same context, outside the timed
+    region) on whole transforms chosen with a fixed seed.  Element samples are fixed seeded index sets, so two runs with the same
+    arguments write the same elements."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    rng = np.random.default_rng(0xD0417)
+
+    def sample(t, count):
+        if t.numel() <= count:
+            return t
+        idx = np.sort(rng.choice(t.numel(), size=count, replace=False))
+        return t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+
+    def save(name, t):
+        np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy().astype(np.float64))
+
+    save("roundtrip", sample(data.view(batch, n), DUMP_ELEMS))
+    k = min(batch, max(1, DUMP_FORWARD_ELEMS // n))
+    rows = torch.from_numpy(np.sort(rng.choice(batch, size=k, replace=False))).to(data.device)
+    fwd = data.view(batch, n)[rows].contiguous()
+    ctx.run_device(fwd.data_ptr(), fwd.data_ptr(), k, False, stream=stream)
+    save("forward", sample(fwd, DUMP_FORWARD_ELEMS))
 
 
 def _oracle_bench_binary():
-    """oracle/build/bench_oracle, rebuilt HERE with gcc -O3 -march=native: the binary is native to the host that
-    times it (the in-tree copy may come from another machine's CPU)."""
+    """bench_oracle, rebuilt HERE with gcc -O3 -march=native: the binary is native to the host that times it.  It is
+    built in a temporary directory removed at exit, never in the tree, which the user running the benchmark may not be able to write."""
+    import atexit
+    import shutil
     import subprocess
-    odir = os.path.join(ROOT, "oracle")
-    exe = os.path.join(odir, "build", "bench_oracle")
-    if os.path.exists(exe):
-        os.remove(exe)
-    subprocess.check_call(["make", "-C", odir, "bench"], stdout=subprocess.DEVNULL)
+    import tempfile
+    tmp = tempfile.mkdtemp(prefix="toyni_bench_oracle_")
+    atexit.register(shutil.rmtree, tmp, ignore_errors=True)
+    exe = os.path.join(tmp, "bench_oracle")
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "bench", f"BENCH={exe}"], stdout=subprocess.DEVNULL)
     return exe
 
 
@@ -686,6 +726,8 @@ def main():
     fence()
     wall = time.perf_counter() - t0
     gpu_s = ev0.elapsed_time(ev1) / 1e3
+    if rank == 0 and args.dump_outputs:     # before the measurement build runs the region again on the same data
+        dump_outputs(args.dump_outputs, ctx, data, batch, n, stream)
     # Kernel durations for the roofline object: the SAME region (same data, same steps) once more through the measurement
     # build of the same source (libtoyni_hip_tools.so), where every pass launch is bracketed by HIP events on the launch stream.
     region, tools_ms_per_step = None, None

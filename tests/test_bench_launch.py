@@ -106,3 +106,41 @@ def test_single_process_slab_line_carries_roofline_and_baseline():
     assert sum(ph.values()) < 3 * out["ms_per_step"]     # one lane's stages: the same order of magnitude as a step (eight lanes share the device)
     assert roof["exchange"]["bytes_sent_per_rank_per_transform"] == 4 * (1 << 25) / 8 * 7 / 8 and "ONE device" in roof["exchange"]["note"]
     assert base["kind"] == "port" and base["cores"] == 1 and base["value"] > 0 and base["extrapolated"] is True and "EXTRAPOLATED" in base["sample"]
+
+
+def test_dump_outputs_and_steps_are_checked_before_any_work():
+    for extra in (["--steps", "0"], ["--dump-outputs", "d", "--workload", "slab"]):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert res.returncode == 2 and "error:" in res.stderr, res.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):
+    """--dump-outputs: float64 arrays of what the timed path computed, identical from two runs with the same arguments; the forward
+    half of the step agrees with the oracle on the transforms the batch held after the last step."""
+    import numpy as np
+    import oracle
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--log-n", "12", "--batch", "8", "--steps", "3", "--warmup", "1",
+                              "--no-extras", "--no-cpu-baseline", "--no-kernel-events", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        out = _last_json(res.stdout)
+        assert out["steps"] == 3 and out["ms_per_step"] > 0
+        assert sorted(os.listdir(d)) == ["forward.npy", "roundtrip.npy"]
+        dumps.append({f: np.load(d / f) for f in ("forward.npy", "roundtrip.npy")})
+    for f, a in dumps[0].items():
+        assert a.dtype == np.float64 and a.shape == (8, 1 << 12) and (a == dumps[1][f]).all(), f
+    rt, fwd = dumps[0]["roundtrip.npy"], dumps[0]["forward.npy"]   # 8 transforms of 2^12: every one is dumped whole
+    for i in range(8):
+        assert (fwd[i].astype(np.uint64) == oracle.ntt(rt[i].astype(np.uint64))).all(), i
+
+
+def test_cpu_baseline_binary_is_built_outside_the_tree():
+    """The benchmark may run as a user who cannot write the tree that build() filled: the host-native timing binary of the
+    cpu_baseline leg goes to a temporary directory."""
+    import bench
+    exe = bench._oracle_bench_binary()
+    assert os.access(exe, os.X_OK) and not os.path.abspath(exe).startswith(ROOT + os.sep), exe

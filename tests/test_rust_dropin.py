@@ -4,7 +4,6 @@ hipcc and ar commands that rust/build.rs would run (parsed out of build.rs, so t
 against the resulting static archive with exactly the libraries build.rs tells cargo to link (reference: build.rs:75-116)."""
 import os
 import re
-import shutil
 import subprocess
 
 import pytest
@@ -43,7 +42,139 @@ def test_build_rs_tracks_every_copied_file():
             assert f in listed, f"toyni_amd/csrc/{f} is missing from INTEGRATION.md section 1 (the crate's hip/ directory would not build)"
 
 
-REFERENCE = "/root/reference"   # present in the build container only (never on the GPU box)
+# A miniature Toyni checkout, written for this test: the layout rust/apply.py works on (Cargo.toml with a [features] table, build.rs,
+# cuda/, src/ntt.rs with a CPU half, the feature-gated `mod cuda` block with its GPU tests nested inside and the re-export behind it,
+# then the CPU tests; src/math/domain.rs calling through crate::ntt::).  The GPU block holds braces inside strings, char literals and
+# comments, so the scanner that locates it is exercised too.
+CHECKOUT_CARGO = """[package]
+name = "toyni"
+version = "0.1.0"
+edition = "2021"
+
+[features]
+default = []
+cuda = []
+
+[dependencies]
+rand = "0.8"
+"""
+
+CHECKOUT_NTT_CPU_HEAD = """use crate::babybear::BabyBear;
+
+pub fn ntt(a: &mut [BabyBear], omega: BabyBear) {
+    let n = a.len();
+    assert!(n.is_power_of_two());
+    let _ = omega;
+}
+
+pub fn intt(a: &mut [BabyBear], omega: BabyBear) {
+    ntt(a, omega.inverse());
+}
+
+"""
+
+CHECKOUT_NTT_GPU_TESTS = """    #[cfg(test)]
+    mod tests {
+        use super::*;
+
+        #[test]
+        fn test_cuda_available() {
+            let _ = cuda_available();
+        }
+
+        #[test]
+        fn test_cuda_ntt_vs_cpu() {
+            if !cuda_available() { return; }
+            let mut a = vec![BabyBear::new(1); 8];
+            ntt_cuda(&mut a, BabyBear::new(1)).unwrap();
+        }
+
+        #[test]
+        fn test_cuda_intt_roundtrip() {
+            if !cuda_available() { return; }
+            let mut a = vec![BabyBear::new(2); 8];
+            intt_cuda(&mut a, BabyBear::new(1)).unwrap();
+        }
+    }
+"""
+
+CHECKOUT_NTT_GPU_BLOCK = """// ---- CUDA backend ----
+#[cfg(feature = "cuda")]
+mod cuda {
+    use super::*;
+
+    #[link(name = "ntt_cuda")]
+    extern "C" {
+        fn ntt_run_inplace(ctx: *mut u8, data: *mut u64, n: usize) -> i32;
+    }
+
+    pub struct CudaBuffer { len: usize }   // not a brace: '}'
+
+    pub fn cuda_available() -> bool {
+        let open = '{';
+        let msg = "unbalanced } in a string {";
+        /* a } in a block comment */
+        open != '}' && !msg.is_empty()
+    }
+
+    pub fn ntt_cuda(a: &mut [BabyBear], _omega: BabyBear) -> Result<(), String> {
+        if a.is_empty() { return Err(String::from("{empty}")); }
+        Ok(())
+    }
+
+    pub fn intt_cuda(a: &mut [BabyBear], omega: BabyBear) -> Result<(), String> {
+        ntt_cuda(a, omega)
+    }
+
+""" + CHECKOUT_NTT_GPU_TESTS + """}
+
+#[cfg(feature = "cuda")]
+pub use cuda::{cuda_available, intt_cuda, ntt_cuda, CudaBuffer};
+"""
+
+CHECKOUT_NTT_CPU_TAIL = """
+#[cfg(test)]
+mod tests {
+    use super::*;
+
+    #[test]
+    fn test_ntt_known_answer() {
+        let mut a = vec![BabyBear::new(1), BabyBear::new(2)];
+        ntt(&mut a, BabyBear::new(1));
+    }
+}
+"""
+
+CHECKOUT_DOMAIN = """use crate::ntt::{intt, ntt};
+
+pub fn fft(values: &mut [crate::babybear::BabyBear], omega: crate::babybear::BabyBear) {
+    #[cfg(feature = "cuda")]
+    {
+        if crate::ntt::cuda_available() && crate::ntt::ntt_cuda(values, omega).is_ok() {
+            return;
+        }
+    }
+    ntt(values, omega);
+}
+
+pub fn ifft(values: &mut [crate::babybear::BabyBear], omega: crate::babybear::BabyBear) {
+    #[cfg(feature = "cuda")]
+    {
+        if crate::ntt::cuda_available() && crate::ntt::intt_cuda(values, omega).is_ok() {
+            return;
+        }
+    }
+    intt(values, omega);
+}
+"""
+
+CHECKOUT_FILES = {
+    "Cargo.toml": CHECKOUT_CARGO,
+    "build.rs": 'fn main() {\n    println!("cargo:rustc-link-lib=static=ntt_cuda");\n}\n',
+    "cuda/ntt_kernel.cu": '// CUDA kernels\nextern "C" int ntt_run_inplace(void*, unsigned long*, unsigned long) { return 0; }\n',
+    "src/ntt.rs": CHECKOUT_NTT_CPU_HEAD + CHECKOUT_NTT_GPU_BLOCK + CHECKOUT_NTT_CPU_TAIL,
+    "src/math/domain.rs": CHECKOUT_DOMAIN,
+}
 
 
 def _load_apply():
@@ -55,13 +186,11 @@ def _load_apply():
 
 
 def _patched_checkout(tmp_path):
-    """A temporary copy of the reference checkout with rust/apply.py applied (build container only)."""
+    """The miniature checkout above, written under tmp_path, with rust/apply.py applied."""
     dst = tmp_path / "toyni_checkout"
-    shutil.copytree(REFERENCE, dst, ignore=shutil.ignore_patterns(".git", "target"))
-    for d, _, names in os.walk(dst):
-        os.chmod(d, 0o755)
-        for n in names:
-            os.chmod(os.path.join(d, n), 0o644)
+    for rel, text in CHECKOUT_FILES.items():
+        (dst / rel).parent.mkdir(parents=True, exist_ok=True)
+        (dst / rel).write_text(text)
     return dst, _load_apply().apply(str(dst))
 
 
@@ -69,18 +198,18 @@ def test_apply_script_lists_the_files_of_integration_md():
     assert sorted(_load_apply().HIP_SOURCES + ["toyni_hip.h"]) == sorted(os.path.basename(f) for f in _integration_file_list())
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="needs the reference checkout (build container only)")
 def test_apply_script_patches_a_reference_checkout_mechanically(tmp_path):
-    """the drop-in as a program.  rust/apply.py on a copy of the reference: the CPU half of src/ntt.rs is untouched, the
-    `mod cuda` block is gone, exactly one real and one stub module took its place, the reference's public names are exported, the
-    call sites of src/math/domain.rs still resolve, the GPU tests nested in the old block were carried over, the feature table and
-    the build script are the new ones, cuda/ is gone and hip/ holds the library."""
+    """the drop-in as a program.  rust/apply.py on a checkout laid out like the reference's: the CPU half of src/ntt.rs
+    is untouched, the `mod cuda` block is gone, exactly one real and one stub module took its place, the reference's public names are
+    exported, the call sites of src/math/domain.rs still resolve, the GPU tests nested in the old block were carried over, the feature
+    table and the build script are the new ones, cuda/ is gone and hip/ holds the library."""
     dst, report = _patched_checkout(tmp_path)
-    ref_ntt = open(os.path.join(REFERENCE, "src", "ntt.rs")).read()
+    ref_ntt = CHECKOUT_FILES["src/ntt.rs"]
     new_ntt = open(dst / "src" / "ntt.rs").read()
     a, b = report["ntt_rs_block_lines"]
     ref_lines, new_lines = ref_ntt.splitlines(keepends=True), new_ntt.splitlines(keepends=True)
-    assert 80 <= a <= 90 and 300 <= b <= 330, (a, b)                      # SURVEY.md 8(a): the GPU wrapper is src/ntt.rs:83-315
+    # the block runs from its banner comment to the re-export behind `mod cuda`
+    assert (a, b) == (CHECKOUT_NTT_CPU_HEAD.count("\n") + 1, (CHECKOUT_NTT_CPU_HEAD + CHECKOUT_NTT_GPU_BLOCK).count("\n")), (a, b)
     assert ref_lines[:a - 1] == new_lines[:a - 1], "the CPU transform above the GPU block must stay byte for byte"
     assert "".join(ref_lines[b:]) == new_ntt[-len("".join(ref_lines[b:])):], "the CPU tests below the GPU block must stay byte for byte"
     assert not re.search(r"^\s*mod cuda\b", new_ntt, flags=re.M) and 'name = "ntt_cuda"' not in new_ntt and "pub use cuda::" not in new_ntt
@@ -92,16 +221,17 @@ def test_apply_script_patches_a_reference_checkout_mechanically(tmp_path):
             assert alias in stmt.split(";")[0], (cfg, alias)
     # every crate::ntt:: name the callers use (src/math/domain.rs:90-97,113-119) is still exported
     dom = open(dst / "src" / "math" / "domain.rs").read()
-    assert dom == open(os.path.join(REFERENCE, "src", "math", "domain.rs")).read(), "the call sites are not edited"
+    assert dom == CHECKOUT_DOMAIN, "the call sites are not edited"
     used = set(re.findall(r"crate::ntt::(\w+)", dom))
     assert used >= {"cuda_available", "ntt_cuda", "intt_cuda"}
     for name in used:
         assert re.search(rf"pub use [^;]*\b(?:as )?{name}\b", new_ntt), f"crate::ntt::{name} no longer resolves"
-    # the reference's three GPU tests (nested in the old block, src/ntt.rs:253-311) were carried over from the checkout into `mod gpu`
-    assert report["carried_test_lines"] >= 40
+    # the three GPU tests nested in the old block were carried over verbatim from the checkout into `mod gpu`
+    assert report["carried_test_lines"] == CHECKOUT_NTT_GPU_TESTS.count("\n")
     gpu_mod = new_ntt[new_ntt.index("mod gpu {"):new_ntt.index("mod gpu_absent {")]
     for t in ("fn test_cuda_available", "fn test_cuda_ntt_vs_cpu", "fn test_cuda_intt_roundtrip"):
         assert t in gpu_mod and t in ref_ntt, t
+    assert CHECKOUT_NTT_GPU_TESTS.rstrip("\n") in gpu_mod
     assert "use self::{gpu_available as cuda_available" in gpu_mod
     # nothing that depends on a recent prelude -- the layout guarantee is spelled as the reference spells it
     # (src/ntt.rs:115-116): `size_of` / `align_of` are prelude items only since Rust 1.80
@@ -110,7 +240,7 @@ def test_apply_script_patches_a_reference_checkout_mechanically(tmp_path):
     assert not re.search(r"(?<![:\w])(?:size_of|align_of)::<", new_ntt), "unqualified size_of / align_of"
     assert new_ntt.count("{") == new_ntt.count("}")
     # Cargo.toml: one [features] table, the new one; everything else as before
-    cargo, ref_cargo = open(dst / "Cargo.toml").read(), open(os.path.join(REFERENCE, "Cargo.toml")).read()
+    cargo, ref_cargo = open(dst / "Cargo.toml").read(), CHECKOUT_CARGO
     assert cargo.count("[features]") == 1 and 'hip = []' in cargo and 'cuda = ["hip"]' in cargo and "cuda = []" not in cargo
     strip = lambda t: re.sub(r"^\[features\]\n(?:(?!\[)[^\n]*\n)*", "", t, flags=re.M).split()
     assert strip(cargo) == strip(ref_cargo)
@@ -123,15 +253,10 @@ def test_apply_script_patches_a_reference_checkout_mechanically(tmp_path):
 
 def test_following_integration_md_produces_a_linkable_archive(tmp_path):
     import __graft_entry__ as entry
-    if os.path.isdir(REFERENCE):
-        # build container: the crate IS a patched copy of the reference (rust/apply.py), so build.rs's commands run in the real layout
-        crate, _ = _patched_checkout(tmp_path)
-    else:
-        crate = tmp_path / "toyni"
-        (crate / "hip").mkdir(parents=True)
-        for f in _integration_file_list():
-            assert os.path.exists(f), f"INTEGRATION.md lists {f}, which does not exist"
-            shutil.copy(f, crate / "hip")
+    for f in _integration_file_list():
+        assert os.path.exists(f), f"INTEGRATION.md lists {f}, which does not exist"
+    # the crate is a checkout patched by rust/apply.py, so build.rs's commands run in the real layout
+    crate, _ = _patched_checkout(tmp_path)
     # every csrc file the translation unit includes must be on the list (a file missing from INTEGRATION.md breaks the crate)
     out = tmp_path / "out"
     out.mkdir()
