@@ -301,7 +301,8 @@ int toyni_poly_eval_device(toyni_ntt_ctx* ctx, const uint32_t* d_coeffs, size_t 
 /* Openings (open_merkle, src/fibonacci.rs:366-375, over MerkleTree::get_proof, src/merkle.rs:50-80) of nidx leaves of a tree built
  * by toyni_merkle_commit_device / toyni_fri_fold_commit_device, gathered on the device into nidx records of
  * toyni_merkle_open_record_bytes(n) bytes each:  depth x 32 path bytes | 16 salt bytes (zero if d_salts is NULL) | the value as
- * 8 LE bytes | depth position bytes (1 = the sibling is the LEFT input), padded to a multiple of 8.  d_out 8-byte aligned. */
+ * 8 LE bytes | depth position bytes (1 = the sibling is the LEFT input), padding zero to a multiple of 8.  Every byte of a
+ * record is written.  d_out 8-byte aligned. */
 size_t toyni_merkle_open_record_bytes(size_t n);
 int toyni_merkle_open_device(const uint8_t* d_levels, size_t n, const uint32_t* d_values, const uint8_t* d_salts, const uint32_t* d_indices,
                              size_t nidx, uint8_t* d_out, void* stream);

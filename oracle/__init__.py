@@ -292,3 +292,18 @@ def merkle_get_proof(levels, index):
     if d < 0:
         return None
     return [path[l].tobytes() for l in range(d)], [bool(pos[l]) for l in range(d)]
+
+
+def merkle_get_proofs(levels, indices):
+    """merkle_get_proof for many indices of one tree, the levels concatenated once (a 2^21-leaf tree is 128 MB, which the
+    single-index form copies per call): a list of (path digests, position flags), None for an index out of range."""
+    n = len(levels[0])
+    flat = np.ascontiguousarray(np.concatenate(levels), dtype=np.uint8)
+    depth = len(levels) - 1
+    path = np.zeros((max(depth, 1), 32), dtype=np.uint8)
+    pos = np.zeros(max(depth, 1), dtype=np.uint8)
+    out = []
+    for index in indices:
+        d = _lib.orc_merkle_get_proof(path.ctypes.data, pos.ctypes.data, flat.ctypes.data, n, int(index))
+        out.append(None if d < 0 else ([path[l].tobytes() for l in range(d)], [bool(pos[l]) for l in range(d)]))
+    return out

@@ -22,10 +22,11 @@ static std::string hex(const uint8_t* p, size_t n) {
     return s;
 }
 
-static bool write_proof(const char* path, const Proof& pr) {
+// key: the 32 bytes the written proof was generated under (it changes with <reps> and --phases); the tests re-derive the proof from it
+static bool write_proof(const char* path, const Proof& pr, const uint8_t key[32]) {
     FILE* f = std::fopen(path, "w");
     if (!f) return false;
-    std::fprintf(f, "{\"trace_len\": %zu, \"lde_size\": %zu, \"trace_commitment\": \"%s\", \"quotient_commitment\": \"%s\",\n", pr.trace_len, pr.lde_size,
+    std::fprintf(f, "{\"key\": \"%s\",\n \"trace_len\": %zu, \"lde_size\": %zu, \"trace_commitment\": \"%s\", \"quotient_commitment\": \"%s\",\n", hex(key, 32).c_str(), pr.trace_len, pr.lde_size,
                  hex(pr.trace_commitment.data(), 32).c_str(), hex(pr.quotient_commitment.data(), 32).c_str());
     std::fprintf(f, " \"t_z\": %u, \"t_gz\": %u, \"t_ggz\": %u, \"q_z\": %u,\n \"fri_commitments\": [", pr.t_z, pr.t_gz, pr.t_ggz, pr.q_z);
     for (size_t i = 0; i < pr.fri_commitments.size(); ++i) std::fprintf(f, "%s\"%s\"", i ? ", " : "", hex(pr.fri_commitments[i].data(), 32).c_str());
@@ -86,7 +87,7 @@ int main(int argc, char** argv) {
         err = prover.generate_proof(trace.data(), key, proof, &pt);
         if (!err.empty()) { std::printf("{\"gpu\": true, \"error\": \"%s\"}\n", err.c_str()); return 1; }
     }
-    if (out_path && !write_proof(out_path, proof)) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; }
+    if (out_path && !write_proof(out_path, proof, key)) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; }
     std::printf("{\"gpu\": true, \"trace_len\": %zu, \"lde_size\": %zu, \"folds\": %zu, \"final_layer_size\": %zu, \"ms\": %s, "
                 "\"phases\": {\"1_interpolate_mask_lde_commit\": %.4f, \"2_constraint_quotient_commit\": %.4f, \"3_transcript_ood\": %.4f, \"5_deep\": %.4f, "
                 "\"6_fri_fold_commit\": %.4f, \"7_queries\": %.4f}, \"proof_bytes\": %zu, "

@@ -112,9 +112,15 @@ def fibonacci_trace(n: int) -> np.ndarray:
     return out
 
 
-def generate_proof(trace_col: np.ndarray, seed: int = 0, stats: dict = None, timing: dict = None, raw: bool = False):
+def _host_u64(t: torch.Tensor) -> np.ndarray:
+    return t.cpu().numpy().view(np.uint32).astype(np.uint64)
+
+
+def generate_proof(trace_col: np.ndarray, seed: int = 0, stats: dict = None, timing: dict = None, raw: bool = False, capture: dict = None):
     """raw=True returns the proof with its openings still in the serialized record form the device wrote (what a prover would
-    put on the wire; `expand_proof` turns it into the field-by-field structure of StarkProof / QueryProof)."""
+    put on the wire; `expand_proof` turns it into the field-by-field structure of StarkProof / QueryProof).
+    capture (tests): a dict that receives host copies of every component, keyed as tests/harness/ref_prover.py keys them, plus
+    the randomness drawn ("salt_pool", and the mask values as "mask").  None leaves the path untouched: no copies, no syncs."""
     import time
     dev = torch.device("cuda", 0)
     _t = [time.perf_counter()]
@@ -173,6 +179,8 @@ def generate_proof(trace_col: np.ndarray, seed: int = 0, stats: dict = None, tim
     c32 = torch.empty(N, dtype=torch.int32, device=dev)
     q32 = torch.empty(N, dtype=torch.int32, device=dev)
     pv.fib_quotient_device(ctx_N, trace_lde.data_ptr(), c32.data_ptr(), q32.data_ptr(), 5, COSET_SHIFT, stream=stream)
+    if capture is not None:                                        # before ifft #1 overwrites c32 in place
+        capture["c_evals"] = _host_u64(c32)
     ntt_dev(ctx_N, c32, True, shift=COSET_SHIFT)                   # ifft #1 (c_poly; re-evaluating it on the coset is the identity)
     q_poly = q32.clone()
     ntt_dev(ctx_N, q_poly, True, shift=COSET_SHIFT)                # ifft #2
@@ -224,6 +232,16 @@ def generate_proof(trace_col: np.ndarray, seed: int = 0, stats: dict = None, tim
             tr.absorb(root)
         return tr.squeeze_challenge() if want_beta else 0
 
+    if capture is not None:                                        # the same callback, recording every beta it hands out
+        capture["betas"] = []
+        squeeze = challenge
+
+        def challenge(_round, root, want_beta):
+            beta = squeeze(_round, root, want_beta)
+            if want_beta:
+                capture["betas"].append(beta)
+            return beta
+
     pv.fri_commit_phase_device(ctx_N, d32.data_ptr(), N, COSET_SHIFT, final_size, salts_all.data_ptr() if salts_all is not None else 0,
                                challenge, layers_all.data_ptr(), levels_all.data_ptr(), stream=stream)
     lo = dlo = slo = 0
@@ -266,6 +284,13 @@ def generate_proof(trace_col: np.ndarray, seed: int = 0, stats: dict = None, tim
     lap("7_queries")
     if stats is not None:
         stats.update({"n": n, "lde": N, "folds": len(layers) - 1, "final_layer_size": final_size})
+    if capture is not None:
+        capture.update({
+            "salt_pool": salt_pool.cpu().numpy(), "mask": [int(v) for v in r.cpu().numpy()],
+            "masked_coeffs": _host_u64(compact[:ncoef_t]), "trace_lde": _host_u64(trace_lde), "q_evals": _host_u64(q32),
+            "c_poly": _host_u64(c32), "q_poly": _host_u64(q_poly), "z": z, "ood": (t_z, t_gz, t_ggz, q_z), "deep": _host_u64(d32),
+            "fri_layers": [_host_u64(layer) for layer in layers[1:]],
+        })
     proof = {
         "trace_len": n, "lde_size": N, "trace_commitment": trace_commitment, "quotient_commitment": quotient_commitment,
         "t_z": t_z, "t_gz": t_gz, "t_ggz": t_ggz, "q_z": q_z, "fri_commitments": commitments, "fri_final_layer": final_layer,

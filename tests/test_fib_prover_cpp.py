@@ -98,15 +98,23 @@ int main() {
 def test_cpp_proof_is_accepted_by_the_verifier_restatement(tmp_path, n, lde, folds, final):
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tests"))
-    from harness import fib_prover, fib_verifier
+    from harness import fib_prover, fib_verifier, ref_prover
     path = tmp_path / "proof.json"
     rc, out = _run([n, 5, 1, path, "--phases"])
     assert rc == 0 and out["gpu"], out
     assert (out["trace_len"], out["lde_size"], out["folds"], out["final_layer_size"]) == (n, lde, folds, final)
-    proof = fib_prover.expand_proof(_load_proof(path))
+    raw = _load_proof(path)
+    proof = fib_prover.expand_proof(raw)
     why = []
     assert fib_verifier.verify(proof, why), why
     assert len(proof["query_proofs"]) == 44 and len(proof["fri_commitments"]) == folds + 1 and len(set(proof["fri_final_layer"])) == 1
+    # byte for byte the reference prover's proof (the oracle alone) under the key the file names: commitments, OOD values, every
+    # FRI commitment, final layer, query indices, the raw opening records of each group.  The roots cover every element of every
+    # committed layer (the quotient tree's leaves are q_evals, whose polynomial q_z evaluates); the records cover every byte the
+    # verifier skips -- padding included
+    want, _ = ref_prover.prove(fib_prover.fibonacci_trace(n), ref_prover.ChaChaRandomness(bytes.fromhex(raw["key"])))
+    diff = ref_prover.first_proof_difference(raw, want)
+    assert not diff, diff
     # tampering is caught on the C++ prover's proofs exactly as on the harness' (src/verifier.rs:303-379)
     bad = dict(proof, t_z=(proof["t_z"] + 1) % fib_verifier.P)
     why = []

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import oracle
+from harness import ref_prover
 from oracle import P
 
 pytestmark = pytest.mark.gpu
@@ -92,7 +93,7 @@ def test_merkle_openings(env, n, salted):
     idx = sorted(set([0, n - 1, n // 2, (n * 7) // 11] + list(np.random.default_rng(1).integers(0, n, 10))))
     it = torch.tensor(idx, dtype=torch.int32, device=dev)
     rec = ta.prover.merkle_open_record_bytes(n)
-    out = torch.zeros(len(idx) * rec, dtype=torch.uint8, device=dev)
+    out = torch.full((len(idx) * rec,), 0xA5, dtype=torch.uint8, device=dev)     # not zeros: every byte of a record must be written
     ta.prover.merkle_open_device(lv.data_ptr(), n, v.data_ptr(), s.data_ptr() if salted else 0, it.data_ptr(), len(idx), out.data_ptr())
     torch.cuda.synchronize()
     ops = ta.prover.parse_openings(out.cpu().numpy(), n, idx, salted)
@@ -100,6 +101,11 @@ def test_merkle_openings(env, n, salted):
         path, pos = oracle.merkle_get_proof(levels_want, o["index"])
         assert o["path"] == path and o["position"] == pos and o["value"] == int(vals[o["index"]])
         assert o["salt"] == (salts[o["index"]].tobytes() if salted else b"")
+    # the raw records, byte for byte: path | salt | value | positions | padding zero (depths 1, 2, 4, 10, 12 leave a pad here)
+    _, want = ref_prover.serialize_openings(levels_want, vals, salts, idx)
+    got = out.cpu().numpy()
+    bad = np.nonzero(got != want)[0]
+    assert not bad.size, f"record {bad[0] // rec}, byte {bad[0] % rec} of {rec}: {got[bad[0]]} != {want[bad[0]]} ({bad.size} bytes differ)"
 
 
 def test_merkle_openings_of_several_trees_in_one_launch(env):

@@ -6,8 +6,7 @@ import copy
 import numpy as np
 import pytest
 
-import oracle
-from harness import fib_verifier
+from harness import fib_verifier, ref_prover
 
 pytestmark = pytest.mark.gpu
 
@@ -79,20 +78,33 @@ def test_invalid_trace_is_caught(prover):
         prover.generate_proof(col, seed=3)
 
 
+def _prove_and_match_the_reference(prover, n, seed, stats=None):
+    """A harness proof, its components captured on the way, against the reference prover (tests/harness/ref_prover.py: the oracle
+    alone) on the same salts and mask: every component in protocol order, then the whole proof, raw opening records included."""
+    cap = {}
+    raw = prover.generate_proof(prover.fibonacci_trace(n), seed=seed, stats=stats, raw=True, capture=cap)
+    want, comp = ref_prover.prove(prover.fibonacci_trace(n), ref_prover.HarnessRandomness(cap["salt_pool"], cap["mask"]))
+    diff = ref_prover.first_component_difference(cap, comp)
+    assert not diff, diff
+    diff = ref_prover.first_proof_difference(raw, want)
+    assert not diff, diff
+    proof = prover.expand_proof(raw)
+    assert proof == {k: want[k] for k in proof}
+    return proof
+
+
 def test_components_match_oracle_on_the_proof_data(prover):
-    # component-level bit-exactness on the same data: the committed trace LDE equals the oracle's coset FFT of
-    # the masked polynomial, and every FRI layer equals the oracle's fri_fold of the previous one -- checked through openings
-    proof = prover.generate_proof(prover.fibonacci_trace(64), seed=4)
+    # component-level bit-exactness on the same data (SURVEY F5b): masked coefficients, trace LDE, constraint and quotient
+    # evaluations and their inverse transforms, z and the OOD values, the DEEP layer, every beta and FRI layer equal the oracle's,
+    # and the proof equals the reference prover's byte for byte
+    proof = _prove_and_match_the_reference(prover, 64, seed=4)
     assert fib_verifier.verify(proof)
-    n, N = 64, 2048
-    assert proof["query_proofs"][0]["trace_opening"]["index"] < N // 2
-    assert oracle.bb_pow(oracle.root_of_unity(6), n) == 1
 
 
 def test_full_size_prove_trace_2_16(prover):
     # BASELINE configs[2]: trace_len 2^16, blowup 32 -> lde 2^21, 17 folds 2^21 -> 2^4
     stats = {}
-    proof = prover.generate_proof(prover.fibonacci_trace(1 << 16), seed=5, stats=stats)
+    proof = _prove_and_match_the_reference(prover, 1 << 16, seed=5, stats=stats)
     assert stats == {"n": 1 << 16, "lde": 1 << 21, "folds": 17, "final_layer_size": 16}
     why = []
     assert fib_verifier.verify(proof, why), why
@@ -103,7 +115,7 @@ def test_trace_len_8_the_readme_table(prover):
     # BASELINE configs[0] names trace_len 8 (the README's 8-row illustration): lde 256, degree bound 256,
     # 8 folds down to a single-element final layer
     stats = {}
-    proof = prover.generate_proof(prover.fibonacci_trace(8), seed=8, stats=stats)
+    proof = _prove_and_match_the_reference(prover, 8, seed=8, stats=stats)
     assert stats == {"n": 8, "lde": 256, "folds": 8, "final_layer_size": 1}
     why = []
     assert fib_verifier.verify(proof, why), why

@@ -123,7 +123,7 @@ TOYNI_HD uint32_t poly_thread_term(const PolyEvalArgs& a, uint32_t p, const uint
 
 // ---- Merkle openings (src/merkle.rs:50-80, src/fibonacci.rs:366-375) ----
 // record of one opening: depth x 32 path bytes | 16 salt bytes (zero when unsalted) | value as 8 LE bytes | depth position bytes
-// (1 = the sibling is the LEFT input of the node hash), padded to a multiple of 8
+// (1 = the sibling is the LEFT input of the node hash), padding zero to a multiple of 8
 TOYNI_HD uint32_t merkle_depth(uint64_t n) {
     uint32_t d = 0;
     while (n > 1) { n = (n + 1) / 2; ++d; }

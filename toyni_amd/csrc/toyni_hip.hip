@@ -729,6 +729,9 @@ __device__ __forceinline__ void merkle_open_group(const OpenGroup& g, uint64_t f
             tail[0] = sv.x; tail[1] = sv.y; tail[2] = sv.z; tail[3] = sv.w;
             tail[4] = g.values[index];
             tail[5] = 0u;
+            // padding zero, so a record is a function of the tree alone: byte stores, clear of the position bytes
+            // [32 depth + 24, 33 depth + 24) that the other threads of this record write
+            for (uint64_t b = (uint64_t)depth * 33u + 24u; b < rec; ++b) r[b] = 0;
         }
     }
 }
