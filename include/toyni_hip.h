@@ -11,6 +11,16 @@
  *   device "u32" : packed uint32_t canonical residues (the native device format; 8 B/element of HBM
  *                  traffic per pass instead of 16).
  *
+ * Pointer alignment of the device entry points.  Every rule above 4 bytes is checked: a pointer that breaks it is refused with
+ * TOYNI_E_RANGE before anything is enqueued (the narrow / widen pair also refuses a u32 pointer below 4 bytes):
+ *   4 bytes  every packed-u32 pointer not listed below: the transforms (plain, coset, Ext, LDE, Ext LDE), domain points, the
+ *            four-step twiddle, the slab pass, the structured and explicit-point folds and the fold loop (16-byte aligned layers of
+ *            whole quads take 16-byte accesses, others word accesses), the fold round's d_evals / d_out, the commit phase's
+ *            d_layer0 / d_layers, quotient, DEEP, polynomial evaluation and its d_out, the openings' d_values / d_indices
+ *   8 bytes  u64 pointers (toyni_ntt_device_u64, the narrow / widen pair) and the openings' d_out
+ *   16 bytes the Ext folds' d_evals / d_out (one 16-byte access per Ext element; d_xs needs 4), the slab relayout's and the fused
+ *            slab rows' d_in / d_out, every Merkle d_levels / d_salts, the ChaCha20 fill's d_out
+ *
  * Threading and streams: a context serialises the ENQUEUEING of its calls with an internal mutex, and keeps its
  * intermediate buffers per stream: calls enqueued on one stream are ordered by that stream, calls enqueued on different
  * streams use different buffers.  So one context may be driven from several host threads and several streams at once
@@ -175,7 +185,7 @@ size_t toyni_first_pass_points(uint32_t n);   /* the same from n alone: no conte
 int toyni_ntt_slab_pass_device(toyni_ntt_ctx* ctx, uint32_t* d_slab, size_t cols_local, size_t col_base, int inverse, void* stream);
 /* W = S1 / parts.  inverse = 0 (after the exchange):  in [parts][rows_local][W] -> out [rows_local][parts][W] = [rows_local][S1];
  * inverse = 1 (before the exchange): in [rows_local][S1] -> out [parts][rows_local][W], times w_n^-((row0 + r) j').
- * Out of place (d_in != d_out). */
+ * Out of place (d_in != d_out), both 16-byte aligned. */
 int toyni_ntt_slab_relayout_device(toyni_ntt_ctx* ctx, const uint32_t* d_in, uint32_t* d_out, size_t rows_local, size_t row0,
                                    size_t parts, int inverse, void* stream);
 /* The relayout and the size-S1 row transforms as ONE step either side of the exchange (round 5), `row_ctx` = a context of size S1 on
@@ -185,7 +195,8 @@ int toyni_ntt_slab_relayout_device(toyni_ntt_ctx* ctx, const uint32_t* d_in, uin
  * Where the pass shapes the launch takes can address the pieces layout, no relayout sweep exists: the first pass of the forward row
  * transforms reads the pieces, the last pass of the inverse ones writes them -- three HBM sweeps per direction around the exchange
  * instead of four; otherwise (a few rows, rows of at most 1024 points, a chunked context) the two steps above run one after the
- * other.  Same results either way; *fused (may be NULL) reports which ran.  Out of place; the inverse form may overwrite d_in. */
+ * other.  Same results either way; *fused (may be NULL) reports which ran.  Out of place; the inverse form may overwrite d_in.
+ * d_in and d_out 16-byte aligned (TOYNI_E_RANGE otherwise, whichever form would run). */
 int toyni_ntt_slab_rows_device(toyni_ntt_ctx* ctx, toyni_ntt_ctx* row_ctx, uint32_t* d_in, uint32_t* d_out, size_t rows_local, size_t row0,
                                size_t parts, int inverse, int* fused, void* stream);
 
@@ -238,7 +249,8 @@ int toyni_fri_fold_host(uint64_t* h_out, const uint64_t* h_evals, size_t len, co
 
 /* Extension-field codewords, fri_fold_ext (src/math/fri.rs:7-25): values and beta in Ext = F_p[X]/(X^4 - 11)
  * (src/ext.rs), points in the base field.  Elements are AoS: 4 consecutive words c0..c3 (u32 on the device, u64 on
- * the host = #[repr(C)] Ext { c: [BabyBear; 4] }).  m / len count ELEMENTS.  beta = 4 canonical coordinates. */
+ * the host = #[repr(C)] Ext { c: [BabyBear; 4] }).  m / len count ELEMENTS.  beta = 4 canonical coordinates.  Device forms: d_evals and
+ * d_out 16-byte aligned (TOYNI_E_RANGE otherwise), d_xs 4-byte. */
 int toyni_fri_fold_ext_device(toyni_ntt_ctx* ctx, const uint32_t* d_evals, uint32_t* d_out, size_t m, const uint32_t beta[4], uint32_t x0, void* stream);
 int toyni_fri_fold_ext_xs_device(const uint32_t* d_evals, const uint32_t* d_xs, uint32_t* d_out, size_t m, const uint32_t beta[4], void* stream);
 int toyni_fri_fold_ext_host(uint64_t* h_out, const uint64_t* h_evals, size_t len, const uint64_t* h_xs, const uint64_t beta[4]);

@@ -11,7 +11,6 @@ tests/test_zz_kernel_coverage.py judges.
 
 Checks per case, bit-exact: sampled transforms of the batch (first, last, one in the middle) against the oracle's
 domain_fft / ntt (src/math/domain.rs:107-123, src/ntt.rs:24-53), and the WHOLE batch through inverse(forward(x)) == x."""
-import ctypes
 import os
 import sys
 
@@ -22,15 +21,18 @@ for _p in (ROOT, os.path.join(ROOT, "tests")):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
+from guarded import GUARD_MIN, Guarded  # noqa: E402
+
 P = 2013265921
 
 
 class Dev:
-    def __init__(self, ta, nbytes):
+    """A guard-banded device buffer (tests/guarded.py): down() and free() fail the case if a call wrote outside the payload."""
+
+    def __init__(self, ta, nbytes, guard):
         self.lib = ta._lib.lib
-        p = ctypes.c_void_p()
-        ta._lib.check(self.lib.toyni_malloc(ctypes.byref(p), max(nbytes, 16)), "malloc")
-        self.ptr = p.value
+        self._g = Guarded(ta, max(nbytes, 16), guard=max(guard, GUARD_MIN))   # guard: one transform (or fold layer) of the case
+        self.ptr = self._g.ptr
 
     def up(self, arr):
         arr = np.ascontiguousarray(arr)
@@ -39,10 +41,11 @@ class Dev:
     def down(self, count):
         out = np.empty(count, dtype=np.uint32)
         assert self.lib.toyni_memcpy_d2h(out.ctypes.data, self.ptr, out.nbytes) == 0
+        self._g.check()
         return out
 
     def free(self):
-        self.lib.toyni_free(self.ptr)
+        self._g.free()
 
 
 def batches_for(log_n, cap_log_elems):
@@ -102,7 +105,7 @@ def run_matrix(ta, oracle, profile="default", log=print):
         n = 1 << log_n
         ctx = ctx_of(log_n)
         x = rng.integers(0, P, size=n * batch, dtype=np.uint32)
-        a, b = Dev(ta, x.nbytes), Dev(ta, x.nbytes)
+        a, b = Dev(ta, x.nbytes, 4 * n), Dev(ta, x.nbytes, 4 * n)
         try:
             a.up(x)
             ctx.run_device(a.ptr, b.ptr, batch, False, shift=shift)
@@ -125,7 +128,7 @@ def run_matrix(ta, oracle, profile="default", log=print):
         n_in = n >> z
         ctx = ctx_of(log_n)
         c = rng.integers(0, P, size=n_in * batch * q, dtype=np.uint32)
-        a, b = Dev(ta, c.nbytes), Dev(ta, 4 * n * batch * q)
+        a, b = Dev(ta, c.nbytes, 4 * n * q), Dev(ta, 4 * n * batch * q, 4 * n * q)
         try:
             a.up(c)
             if ext:
@@ -147,7 +150,7 @@ def run_matrix(ta, oracle, profile="default", log=print):
         n = 1 << log_n
         ctx = ctx_of(log_n)
         x = rng.integers(0, P, size=4 * n * batch, dtype=np.uint32)
-        a, b = Dev(ta, x.nbytes), Dev(ta, x.nbytes)
+        a, b = Dev(ta, x.nbytes, 16 * n), Dev(ta, x.nbytes, 16 * n)
         try:
             a.up(x)
             ctx.run_device_ext_batch(a.ptr, b.ptr, batch, False, shift=shift)
@@ -200,7 +203,7 @@ def run_matrix(ta, oracle, profile="default", log=print):
     for m in (1 << 12, 1 << 16):
         ctx = ctx_of(16)
         e = rng.integers(0, P, size=m, dtype=np.uint32)
-        a, o = Dev(ta, e.nbytes), Dev(ta, e.nbytes // 2)
+        a, o = Dev(ta, e.nbytes, e.nbytes), Dev(ta, e.nbytes // 2, e.nbytes)
         try:
             a.up(e)
             ta.fri_fold_device(ctx, a.ptr, o.ptr, m, 424242, 7)
@@ -216,7 +219,7 @@ def run_matrix(ta, oracle, profile="default", log=print):
     e = rng.integers(0, P, size=m, dtype=np.uint32)
     xs = rng.integers(1, P, size=m // 2, dtype=np.uint32)
     xs[[3, 3 + 1024, m // 2 - 1]] = 0
-    a, x, o = Dev(ta, e.nbytes), Dev(ta, xs.nbytes), Dev(ta, e.nbytes // 2)
+    a, x, o = Dev(ta, e.nbytes, e.nbytes), Dev(ta, xs.nbytes, e.nbytes), Dev(ta, e.nbytes // 2, e.nbytes)
     try:
         a.up(e); x.up(xs)
         ta.fri_fold_xs_device(a.ptr, x.ptr, o.ptr, m, 424242)

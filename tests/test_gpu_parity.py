@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import oracle
+from guarded import GUARD_MIN, Guarded
 from oracle import P
 
 pytestmark = pytest.mark.gpu
@@ -31,13 +32,14 @@ def ta():
 
 
 class DevBuf:
-    """Raw device allocation through the ABI's plumbing calls."""
+    """Raw device allocation through the ABI's plumbing calls, guard-banded (tests/guarded.py): download() and free() fail the test
+    if a call wrote before or past the bytes asked for.  Each guard is the whole buffer up to 512 MiB (one transform of the largest
+    size, n = 2^27), or `guard` bytes where the caller knows its transform."""
 
-    def __init__(self, ta, nbytes):
+    def __init__(self, ta, nbytes, guard=None):
         self.lib = ta._lib.lib
-        p = ctypes.c_void_p()
-        ta._lib.check(self.lib.toyni_malloc(ctypes.byref(p), max(nbytes, 4)), "malloc")
-        self.ptr = p.value
+        self._g = Guarded(ta, max(nbytes, 4), guard=guard or min(max(nbytes, GUARD_MIN), 512 << 20))
+        self.ptr = self._g.ptr
         self.nbytes = nbytes
 
     def upload(self, arr, offset=0):
@@ -47,12 +49,13 @@ class DevBuf:
     def download(self, dtype, count, offset=0):
         out = np.empty(count, dtype=dtype)
         assert self.lib.toyni_memcpy_d2h(out.ctypes.data, self.ptr + offset, out.nbytes) == 0
+        self._g.check()
         return out
 
     def free(self):
         if self.ptr:
-            self.lib.toyni_free(self.ptr)
             self.ptr = None
+            self._g.free()
 
 
 def dev_transform(ta, x32, n, batch, inverse, inplace=True, shift=1, chunk=None):
@@ -434,7 +437,7 @@ def test_full_size_ext_vectors(ta, log_n, vecs):
     rng = np.random.default_rng(2700 + log_n)
     x = rng.integers(0, P, size=(vecs, n, 4), dtype=np.uint32)
     ctx = ta.ntt.get_or_create_ctx(n)
-    a, b = DevBuf(ta, x.nbytes), DevBuf(ta, x.nbytes)
+    a, b = DevBuf(ta, x.nbytes, guard=16 * n), DevBuf(ta, x.nbytes, guard=16 * n)     # one Ext vector: up to 2 GiB
     try:
         a.upload(x)
         ctx.run_device_ext_batch(a.ptr, b.ptr, vecs, False)
@@ -457,7 +460,7 @@ def test_batch_1024_x_2_20(ta):
     n, batch, block = 1 << 20, 1024, 32
     ctx = ta.ntt.get_or_create_ctx(n)
     xb = oracle.splitmix(n * block, 91).astype(np.uint32)       # 32 distinct transforms, tiled 32x
-    buf = DevBuf(ta, n * batch * 4)
+    buf = DevBuf(ta, n * batch * 4, guard=4 * n)
     for r in range(batch // block):
         buf.upload(xb, offset=r * xb.nbytes)
     ctx.run_device(buf.ptr, buf.ptr, batch, False)
@@ -484,7 +487,7 @@ def test_batches_beyond_4_gib(ta, log_n, batch):
     per_block = block_elems // n
     xb = oracle.splitmix(block_elems, 95 + log_n).astype(np.uint32)
     total = n * batch
-    buf = DevBuf(ta, total * 4)
+    buf = DevBuf(ta, total * 4, guard=4 * n)
     off = 0
     while off < total:
         m = min(block_elems, total - off)

@@ -484,6 +484,12 @@ __global__ void __launch_bounds__(256) domain_elements_kernel(uint32_t* __restri
 }
 
 
+// whole quads behind 16-byte aligned pointers: the condition under which the structured folds take 16-byte accesses (the entry points
+// accept any 4-byte aligned pointer; a layer of the fold-layers loop starts wherever the one before it ended)
+__host__ __device__ __forceinline__ bool fold_quads(const uint32_t* evals, const uint32_t* out, uint64_t half) {
+    return (half & 3) == 0 && !(((uintptr_t)evals | (uintptr_t)out) & 15);
+}
+
 // FRI fold, structured points; 4 outputs per thread through 16-byte accesses when the layer allows.
 // NT: non-temporal accesses for layers far larger than the Infinity Cache (read once, written once).
 // COMMIT: the same sweep also hashes the leaves of the FOLDED layer's Merkle tree (src/fibonacci.rs:233-241: the layer is
@@ -495,7 +501,7 @@ __global__ void __launch_bounds__(256) fri_fold_kernel(const FoldArgs f, const u
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     // COMMIT: one output and one leaf hash per thread (a SHA-256 compression is ~1 500 instructions against ~20 for the fold:
     // the sweep is hash-bound, so it is kept as wide as the separate leaf kernel)
-    if (!COMMIT && (half & 3) == 0) {
+    if (!COMMIT && fold_quads(f.evals, f.out, half)) {
         const uint4* ea = reinterpret_cast<const uint4*>(f.evals);
         const uint4* eb = reinterpret_cast<const uint4*>(f.evals + half);
         uint4* o = reinterpret_cast<uint4*>(f.out);
@@ -611,7 +617,7 @@ __global__ void __launch_bounds__(256) fib_quotient_kernel(const QuotientArgs a)
     __syncthreads();
     const uint64_t N = (uint64_t)1 << a.log_N, mask = N - 1;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    if (a.log_blowup >= 2 && a.log_N >= 2) {
+    if (a.log_blowup >= 2 && a.log_N >= 2 && !(((uintptr_t)a.trace | (uintptr_t)a.c_out | (uintptr_t)a.q_out) & 15)) {
         const uint4* tr = reinterpret_cast<const uint4*>(a.trace);
         for (uint64_t qd = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; qd < N / 4; qd += stride) {
             const uint64_t i = 4 * qd;
@@ -1894,6 +1900,7 @@ int toyni_lde_host(toyni_ntt_ctx* c, const uint64_t* h_coeffs, size_t ncoeffs, u
 
 int toyni_ntt_device_u64(toyni_ntt_ctx* c, uint64_t* d_data, size_t batch, int inverse, void* stream) {
     if (!c || !d_data) return TOYNI_E_NULL;
+    if ((uintptr_t)d_data & 7) return TOYNI_E_RANGE;   // u64 elements
     TOYNI_CTX_LOCK(c);
     DeviceGuard guard(c->device);
     hipStream_t s = (hipStream_t)stream;
@@ -2169,7 +2176,7 @@ int toyni_ntt_slab_pass_device(toyni_ntt_ctx* c, uint32_t* d_slab, size_t cols_l
 int toyni_ntt_slab_relayout_device(toyni_ntt_ctx* c, const uint32_t* d_in, uint32_t* d_out, size_t rows_local, size_t row0, size_t parts,
                                    int inverse, void* stream) {
     if (!c || !d_in || !d_out) return TOYNI_E_NULL;
-    if (d_in == d_out) return TOYNI_E_RANGE;
+    if (d_in == d_out || (((uintptr_t)d_in | (uintptr_t)d_out) & 15)) return TOYNI_E_RANGE;   // 16-byte accesses on both sides
     const size_t m1 = toyni_ntt_ctx_first_pass_points(c);
     if (!m1) return TOYNI_E_INVALID_SIZE;
     const size_t s1 = (size_t)c->n / m1;
@@ -2201,7 +2208,7 @@ int toyni_ntt_slab_rows_device(toyni_ntt_ctx* big, toyni_ntt_ctx* row, uint32_t*
                                size_t parts, int inverse, int* fused_out, void* stream) {
     if (fused_out) *fused_out = 0;
     if (!big || !row || !d_in || !d_out) return TOYNI_E_NULL;
-    if (d_in == d_out) return TOYNI_E_RANGE;
+    if (d_in == d_out || (((uintptr_t)d_in | (uintptr_t)d_out) & 15)) return TOYNI_E_RANGE;   // (the relayout's 16-byte accesses)
     const size_t m1 = toyni_ntt_ctx_first_pass_points(big);
     if (!m1) return TOYNI_E_INVALID_SIZE;
     const size_t s1 = (size_t)big->n / m1;
@@ -2310,13 +2317,14 @@ static int enqueue_fold(toyni_ntt_ctx* c, const uint32_t* d_evals, uint32_t* d_o
     FoldArgs f;
     int rc = fold_args(c, d_evals, d_out, m, beta, x0, f);
     if (rc) return rc;
-    const size_t work = (d_leaves || (f.half & 3)) ? f.half : f.half / 4;
+    const bool quads = !d_leaves && fold_quads(d_evals, d_out, f.half);
+    const size_t work = quads ? f.half / 4 : f.half;
     const uint4* no_salts = nullptr;
     Digest* no_leaves = nullptr;
     if (d_leaves) {
         hipLaunchKernelGGL((fri_fold_kernel<false, true>), dim3(grid_for(work)), dim3(256), 0, s, f, reinterpret_cast<const uint4*>(d_salts),
                            reinterpret_cast<Digest*>(d_leaves));
-    } else if ((f.half & 3) == 0 && m >= 64 && (uint64_t)m * sizeof(uint32_t) >= fold_nt_min_bytes()) {
+    } else if (quads && m >= 64 && (uint64_t)m * sizeof(uint32_t) >= fold_nt_min_bytes()) {
         // layers beyond the Infinity Cache (>= 256 MiB of input): the shaped stream, 1024 threads x 2 load pairs in flight, non-temporal.
         // A cache-resident 2^24 layer is 5 % FASTER on the 256-thread kernel below (5.95 against 5.63 TB/s), so smaller layers keep it.
         // Measured on a 2^27 layer, alternating (profiles/r03_ab_fold_shape.txt): 5.45-5.47 TB/s for round 2's 256-thread kernel with
@@ -2422,6 +2430,7 @@ int toyni_fri_fold_ext_device(toyni_ntt_ctx* c, const uint32_t* d_evals, uint32_
     if (m == 0) return TOYNI_OK;
     if (!is_pow2(m) || m > c->n) return TOYNI_E_RANGE;
     if (x0 == 0) return TOYNI_E_ZERO_INVERSE;
+    if (((uintptr_t)d_evals | (uintptr_t)d_out) & 15) return TOYNI_E_RANGE;   // one 16-byte access per Ext element
     FoldExtArgs fa{};
     if (x0 >= BB_P || !ext_beta_half(beta, &fa.beta_half)) return TOYNI_E_RANGE;
     TOYNI_CTX_LOCK(c);
@@ -2450,7 +2459,7 @@ int toyni_fri_fold_ext_xs_device(const uint32_t* d_evals, const uint32_t* d_xs, 
     if (m % 2) return TOYNI_E_ODD_LENGTH;
     if (m == 0) return TOYNI_OK;
     ExtFactor f;
-    if (!ext_beta_half(beta, &f)) return TOYNI_E_RANGE;
+    if (!ext_beta_half(beta, &f) || (((uintptr_t)d_evals | (uintptr_t)d_out) & 15)) return TOYNI_E_RANGE;   // 16-byte Ext accesses
     const uint64_t half = m / 2;
     hipLaunchKernelGGL(fri_fold_ext_xs_kernel, dim3(grid_for((half + 3) / 4)), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<const uint4*>(d_evals), d_xs, reinterpret_cast<uint4*>(d_out), half, f);
@@ -2728,7 +2737,8 @@ int toyni_fib_quotient_device(toyni_ntt_ctx* c, const uint32_t* d_trace_lde, uin
         uint32_t t = bb_pow_host(shift, n);
         if (bb_pow_host(t, 1ull << log_blowup) == 1u) return TOYNI_E_ZERO_INVERSE;
     }
-    const uint64_t items = (log_blowup >= 2 && log_N >= 2) ? (1ull << log_N) / 4 : (1ull << log_N);
+    const bool quads = log_blowup >= 2 && log_N >= 2 && !(((uintptr_t)d_trace_lde | (uintptr_t)d_c_evals | (uintptr_t)d_q_evals) & 15);
+    const uint64_t items = quads ? (1ull << log_N) / 4 : (1ull << log_N);   // (the kernel makes the same choice)
     hipLaunchKernelGGL(fib_quotient_kernel, dim3(grid_for(items)), dim3(256), 0, (hipStream_t)stream, a);
     return (int)hipGetLastError();
 }
@@ -2866,6 +2876,7 @@ int toyni_chacha20_fill_device(void* d_out, size_t bytes, const uint8_t key[32],
 
 int toyni_narrow_u64_to_u32(const uint64_t* d_in, uint32_t* d_out, size_t count, void* stream) {
     if (!d_in || !d_out) return TOYNI_E_NULL;
+    if (((uintptr_t)d_in & 7) || ((uintptr_t)d_out & 3)) return TOYNI_E_RANGE;
     if (!count) return TOYNI_OK;
     hipLaunchKernelGGL(narrow_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, d_in, d_out, count);
     return (int)hipGetLastError();
@@ -2873,6 +2884,7 @@ int toyni_narrow_u64_to_u32(const uint64_t* d_in, uint32_t* d_out, size_t count,
 
 int toyni_widen_u32_to_u64(const uint32_t* d_in, uint64_t* d_out, size_t count, void* stream) {
     if (!d_in || !d_out) return TOYNI_E_NULL;
+    if (((uintptr_t)d_in & 3) || ((uintptr_t)d_out & 7)) return TOYNI_E_RANGE;
     if (!count) return TOYNI_OK;
     hipLaunchKernelGGL(widen_kernel, dim3(grid_for(count)), dim3(256), 0, (hipStream_t)stream, d_in, d_out, count);
     return (int)hipGetLastError();
