@@ -6,11 +6,17 @@ of the per-GPU batch is taken forward and back (forward NTT + inverse NTT, BASEL
 n = 2^20; the batch is the repeated-prover workload of configs[3] (1024 transforms per GPU, sharded over
 ranks with no collective -- weak scaling).  value = transforms * n / seconds, whole job.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--batch 1024]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--log-n 20] [--batch 1024] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Rank 0 prints ONE JSON line.  torch is plumbing here (device memory, streams, torch.distributed); the
-compute is libtoyni_hip.so through the C ABI.  The oracle is used only for the cpu_baseline leg.
+compute is libtoyni_hip.so through the C ABI.  The oracle is used only for the cpu_baseline leg and the checks.
+
+A plain run does only what `value` needs: set-up, warm-up, the timed steps, --dump-outputs if given, the line.
+--full adds everything else, after the timed steps: the round-trip and oracle checks, the roofline object (kernel
+durations from a run of the measurement build), the side measurements of other sizes and entry points (extras),
+the CPU baseline, and the multi-device workloads' exchange check and per-phase times.  --no-extras,
+--no-cpu-baseline and --no-kernel-events leave parts of that out again.
 """
 import argparse
 import json
@@ -36,12 +42,15 @@ def parse():
                     help="weak (DEFAULT; the driver's contract): --batch transforms on EVERY GPU.  strong: BASELINE configs[3] as written "
                          "(SURVEY 8(d) C4): --batch transforms in the whole job, batch/N per GPU (ranks < batch mod N take one more)")
     ap.add_argument("--chunk-elems", type=int, default=-1, help="override the context's batch chunking (-1: library default)")
-    ap.add_argument("--no-extras", action="store_true", help="skip single-transform / fold / host-path side measurements")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the checks, the roofline, the side measurements and the CPU baseline "
+                         "(a plain run measures `value` only)")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip single-transform / fold / host-path side measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--chunks", type=int, default=1, help="slab workload: issue the exchange in this many asynchronous pieces")
     ap.add_argument("--no-kernel-events", action="store_true",
-                    help="do not bracket the pass launches of the timed region with HIP events (A/B check of their cost)")
+                    help="--full: do not bracket the pass launches of the timed region with HIP events (A/B check of their cost)")
     ap.add_argument("--probe-ranks", action="store_true",
                     help="launch check without a GPU: the ranks rendezvous over gloo, count themselves and exit (tests/test_bench_launch.py)")
     ap.add_argument("--exchange", choices=["peer", "rccl"], default="peer", help="slab-sp workload: how the one exchange moves its blocks")
@@ -231,7 +240,7 @@ def bench_fourstep(args, dev, rank, world, distributed):
     gen.manual_seed(0x4057E9 + rank)
     cols = torch.randint(0, P, ((1 << l1), (1 << l2) // world), dtype=torch.int32, device=dev, generator=gen)
 
-    keep = cols.clone()
+    keep = cols.clone() if args.full else None
 
     state = {"slab": cols}
 
@@ -257,54 +266,53 @@ def bench_fourstep(args, dev, rank, world, distributed):
     fence()
     own_wall = time.perf_counter() - t0
     wall = tdist.max_over_ranks(own_wall, dev)
-    assert torch.equal(back, keep), "round trip changed the data"
     backend = os.environ.get("TOYNI_BENCH_BACKEND", "nccl")
     ranks_table = gather_rank_table(torch, dist if distributed else None, dev, dev, rank, world, distributed, 2, own_wall, args.steps, backend)
-    # A round trip is the identity for many wrong exchanges too: the FORWARD half is gathered on rank 0 and compared with the
-    # single-device transform of the gathered input (the first run on real links checks itself; outside the timed region).
-    fwd = tdist.slab_forward(keep.clone(), log_n, ops, rank, world, chunks=args.chunks) if slab else tdist.fourstep_forward(keep, log_n, ops, rank, world)
-    ins = [torch.empty_like(keep) for _ in range(world)]
-    outs = [torch.empty_like(fwd) for _ in range(world)]
-    if distributed:
-        dist.all_gather(ins, keep.contiguous())
-        dist.all_gather(outs, fwd.contiguous())
-    else:
-        ins, outs = [keep], [fwd]
-    verified = None
-    if rank == 0:
-        in_index = tdist.slab_input_index if slab else tdist.fourstep_input_index
-        out_index = tdist.slab_output_index if slab else tdist.fourstep_output_index
-        x = torch.empty(1 << log_n, dtype=torch.int32, device=dev)
-        for g in range(world):
-            x[in_index(log_n, world, g).to(dev).reshape(-1)] = ins[g].reshape(-1)
-        ops.big.run_device(x.data_ptr(), x.data_ptr(), 1, False, stream=torch.cuda.current_stream(dev).cuda_stream)
-        torch.cuda.synchronize()
-        verified = all(torch.equal(outs[h].reshape(-1), x[out_index(log_n, world, h).to(dev).reshape(-1)]) for h in range(world))
-        assert verified, "the distributed forward transform differs from the single-device transform"
-        del x
-    del ins, outs, fwd
-    # per-phase times (slab pass / exchange / relayout / rows ...): three more steps with a HIP event between the stages, every rank
-    # runs them (the exchange is collective), rank 0 reports its own
-    phases = None
-    if args.chunks <= 1 or not slab:
-        clock = tdist.PhaseClock(dev)
-        psteps = 3
-        cur = keep.clone()
-        for _ in range(psteps):
-            if slab:
-                out_p = tdist.slab_forward(cur, log_n, ops, rank, world, clock=clock)
-                cur = tdist.slab_inverse(out_p, log_n, ops, rank, world, clock=clock)
-            else:
-                out_p = tdist.fourstep_forward(cur, log_n, ops, rank, world, clock=clock)
-                cur = tdist.fourstep_inverse(out_p, log_n, ops, rank, world, clock=clock)
-        phases = {k: v / psteps for k, v in clock.ms().items()}
-        del cur
-    roof, base = None, None
-    if rank == 0:
-        roof = multi_device_roofline(log_n, world, len({r["pci"] for r in ranks_table}) if backend == "nccl" else 1, wall / args.steps, phases,
-                                     "all_to_all_single over %s" % (dist.get_backend() if distributed else "one rank: identity"))
-        if not args.no_cpu_baseline:
-            base = single_transform_cpu_baseline(log_n)
+    verified, phases, roof, base = None, None, None, None
+    if args.full:
+        assert torch.equal(back, keep), "round trip changed the data"
+        # A round trip is the identity for many wrong exchanges too: the FORWARD half is gathered on rank 0 and compared with the
+        # single-device transform of the gathered input (the first run on real links checks itself; outside the timed region).
+        fwd = tdist.slab_forward(keep.clone(), log_n, ops, rank, world, chunks=args.chunks) if slab else tdist.fourstep_forward(keep, log_n, ops, rank, world)
+        ins = [torch.empty_like(keep) for _ in range(world)]
+        outs = [torch.empty_like(fwd) for _ in range(world)]
+        if distributed:
+            dist.all_gather(ins, keep.contiguous())
+            dist.all_gather(outs, fwd.contiguous())
+        else:
+            ins, outs = [keep], [fwd]
+        if rank == 0:
+            in_index = tdist.slab_input_index if slab else tdist.fourstep_input_index
+            out_index = tdist.slab_output_index if slab else tdist.fourstep_output_index
+            x = torch.empty(1 << log_n, dtype=torch.int32, device=dev)
+            for g in range(world):
+                x[in_index(log_n, world, g).to(dev).reshape(-1)] = ins[g].reshape(-1)
+            ops.big.run_device(x.data_ptr(), x.data_ptr(), 1, False, stream=torch.cuda.current_stream(dev).cuda_stream)
+            torch.cuda.synchronize()
+            verified = all(torch.equal(outs[h].reshape(-1), x[out_index(log_n, world, h).to(dev).reshape(-1)]) for h in range(world))
+            assert verified, "the distributed forward transform differs from the single-device transform"
+            del x
+        del ins, outs, fwd
+        # per-phase times (slab pass / exchange / relayout / rows ...): three more steps with a HIP event between the stages, every rank
+        # runs them (the exchange is collective), rank 0 reports its own
+        if args.chunks <= 1 or not slab:
+            clock = tdist.PhaseClock(dev)
+            psteps = 3
+            cur = keep.clone()
+            for _ in range(psteps):
+                if slab:
+                    out_p = tdist.slab_forward(cur, log_n, ops, rank, world, clock=clock)
+                    cur = tdist.slab_inverse(out_p, log_n, ops, rank, world, clock=clock)
+                else:
+                    out_p = tdist.fourstep_forward(cur, log_n, ops, rank, world, clock=clock)
+                    cur = tdist.fourstep_inverse(out_p, log_n, ops, rank, world, clock=clock)
+            phases = {k: v / psteps for k, v in clock.ms().items()}
+            del cur
+        if rank == 0:
+            roof = multi_device_roofline(log_n, world, len({r["pci"] for r in ranks_table}) if backend == "nccl" else 1, wall / args.steps, phases,
+                                         "all_to_all_single over %s" % (dist.get_backend() if distributed else "one rank: identity"))
+            if not args.no_cpu_baseline:
+                base = single_transform_cpu_baseline(log_n)
     if rank == 0:
         print(json.dumps({
             "exchange_verified": verified, "ranks": ranks_table,
@@ -404,7 +412,8 @@ def bench_slab_single_process(args):
         gen.manual_seed(0x51AB + g)
         slabs.append(torch.randint(0, P, (n // lanes,), dtype=torch.int32, device=dev, generator=gen))
         rows.append(torch.empty(n // lanes, dtype=torch.int32, device=dev))
-        keep.append(slabs[-1].clone())
+        if args.full:
+            keep.append(slabs[-1].clone())
     sp, rp = [t.data_ptr() for t in slabs], [t.data_ptr() for t in rows]
 
     def step():
@@ -419,40 +428,40 @@ def bench_slab_single_process(args):
     for _ in range(args.steps):
         step()                                   # the entry point blocks until every lane is done
     wall = time.perf_counter() - t0
-    assert all(torch.equal(a, b) for a, b in zip(slabs, keep)), "round trip changed the data"
-    # the forward half against the single-device transform (a round trip alone is the identity for many wrong exchanges): gather the
-    # input in natural order, transform it on device 0 alone, compare every lane's row block
-    verified = None
-    if log_n <= 27:
-        d0 = torch.device("cuda", devices[0])
-        nat = torch.empty(n, dtype=torch.int32, device=d0)
-        for g in range(lanes):
-            nat[tdist.slab_input_index(log_n, lanes, g).to(d0).reshape(-1)] = keep[g].to(d0)
-        one = toyni_amd.NttContext(n, device=devices[0])
-        one.run_device(nat.data_ptr(), nat.data_ptr(), 1, False, stream=torch.cuda.current_stream(d0).cuda_stream)
-        torch.cuda.synchronize(d0)
-        toyni_amd.ntt_slab_multi_gpu_device(n, devices, sp, rp, False, exchange)
-        verified = all(torch.equal(rows[h].to(d0), nat[tdist.slab_output_index(log_n, lanes, h).to(d0).reshape(-1)]) for h in range(lanes))
-        assert verified, "multi-device forward transform differs from the single-device transform"
-        del nat
-    # where a step's time goes: three more steps through the measurement build of the same source, whose lane 0 carries an event
-    # between the four stages (toyni_tools_slab_phases; one-piece exchanges only) -- in a CHILD process: the measured
-    # process never holds a second copy of the library with its own contexts, exchange buffers and communicators, and nothing that
-    # goes wrong there (build, out of memory, RCCL start-up) can take the already measured line down with it
-    phases = None
-    try:
-        import subprocess
-        slabs.clear(); rows.clear(); keep.clear()      # this process's buffers are no longer needed: the child allocates its own
-        torch.cuda.empty_cache()
-        res = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", "slab-sp", "--slab-phases-child", "--log-n", str(log_n),
-                              "--gpus", str(lanes), "--exchange", args.exchange], capture_output=True, text=True, timeout=600)
-        line = [l for l in res.stdout.splitlines() if l.startswith('{"slab_phases"')]
-        if res.returncode == 0 and line:
-            phases = json.loads(line[-1])["slab_phases"]
-        else:
-            print(f"bench.py: per-phase times unavailable (child status {res.returncode}): {res.stderr[-400:]}", file=sys.stderr)
-    except Exception as exc:                        # the line goes out without the per-phase times
-        print(f"bench.py: per-phase times unavailable ({type(exc).__name__}: {exc})", file=sys.stderr)
+    verified, phases = None, None
+    if args.full:
+        assert all(torch.equal(a, b) for a, b in zip(slabs, keep)), "round trip changed the data"
+        # the forward half against the single-device transform (a round trip alone is the identity for many wrong exchanges): gather the
+        # input in natural order, transform it on device 0 alone, compare every lane's row block
+        if log_n <= 27:
+            d0 = torch.device("cuda", devices[0])
+            nat = torch.empty(n, dtype=torch.int32, device=d0)
+            for g in range(lanes):
+                nat[tdist.slab_input_index(log_n, lanes, g).to(d0).reshape(-1)] = keep[g].to(d0)
+            one = toyni_amd.NttContext(n, device=devices[0])
+            one.run_device(nat.data_ptr(), nat.data_ptr(), 1, False, stream=torch.cuda.current_stream(d0).cuda_stream)
+            torch.cuda.synchronize(d0)
+            toyni_amd.ntt_slab_multi_gpu_device(n, devices, sp, rp, False, exchange)
+            verified = all(torch.equal(rows[h].to(d0), nat[tdist.slab_output_index(log_n, lanes, h).to(d0).reshape(-1)]) for h in range(lanes))
+            assert verified, "multi-device forward transform differs from the single-device transform"
+            del nat
+        # where a step's time goes: three more steps through the measurement build of the same source, whose lane 0 carries an event
+        # between the four stages (toyni_tools_slab_phases; one-piece exchanges only) -- in a CHILD process: the measured
+        # process never holds a second copy of the library with its own contexts, exchange buffers and communicators, and nothing that
+        # goes wrong there (build, out of memory, RCCL start-up) can take the already measured line down with it
+        try:
+            import subprocess
+            slabs.clear(); rows.clear(); keep.clear()      # this process's buffers are no longer needed: the child allocates its own
+            torch.cuda.empty_cache()
+            res = subprocess.run([sys.executable, os.path.abspath(__file__), "--workload", "slab-sp", "--slab-phases-child", "--log-n", str(log_n),
+                                  "--gpus", str(lanes), "--exchange", args.exchange], capture_output=True, text=True, timeout=600)
+            line = [l for l in res.stdout.splitlines() if l.startswith('{"slab_phases"')]
+            if res.returncode == 0 and line:
+                phases = json.loads(line[-1])["slab_phases"]
+            else:
+                print(f"bench.py: per-phase times unavailable (child status {res.returncode}): {res.stderr[-400:]}", file=sys.stderr)
+        except Exception as exc:                        # the line goes out without the per-phase times
+            print(f"bench.py: per-phase times unavailable ({type(exc).__name__}: {exc})", file=sys.stderr)
     pci = {}
     for d in sorted(set(devices)):
         pr = torch.cuda.get_device_properties(d)
@@ -467,8 +476,9 @@ def bench_slab_single_process(args):
                                f"single process, exchange by {'RCCL grouped send/recv' if args.exchange == 'rccl' else 'hipMemcpyPeerAsync'}",
                    "log_n": log_n, "parallelism": f"column/row split x{lanes}, one exchange"},
         "roofline": multi_device_roofline(log_n, lanes, len(set(devices)), wall / args.steps, phases,
-                                          "RCCL grouped send/recv" if args.exchange == "rccl" else "hipMemcpyPeerAsync, one copy stream per source"),
-        "cpu_baseline": None if args.no_cpu_baseline else single_transform_cpu_baseline(log_n)}))
+                                          "RCCL grouped send/recv" if args.exchange == "rccl" else "hipMemcpyPeerAsync, one copy stream per source")
+                    if args.full else None,
+        "cpu_baseline": single_transform_cpu_baseline(log_n) if args.full and not args.no_cpu_baseline else None}))
 
 
 def shard_batch(total, world, rank, scaling):
@@ -677,7 +687,8 @@ def main():
     import __graft_entry__ as entry
     if rank == 0:
         entry.build_hip()
-        entry.build_tools()
+        if args.full:
+            entry.build_tools()
     if distributed:
         dist.barrier()
     import toyni_amd
@@ -701,7 +712,7 @@ def main():
     for off in range(0, batch * n, piece):
         m = min(piece, batch * n - off)
         data[off:off + m] = torch.randint(0, P, (m,), dtype=torch.int32, device=dev, generator=gen)
-    check_before = data.clone()          # the WHOLE batch: forward + inverse must leave every transform unchanged
+    check_before = data.clone() if args.full else None   # the WHOLE batch: forward + inverse must leave every transform unchanged
     stream = torch.cuda.current_stream().cuda_stream
     ptr = data.data_ptr()
 
@@ -731,7 +742,7 @@ def main():
     # Kernel durations for the roofline object: the SAME region (same data, same steps) once more through the measurement
     # build of the same source (libtoyni_hip_tools.so), where every pass launch is bracketed by HIP events on the launch stream.
     region, tools_ms_per_step = None, None
-    if rank == 0 and not args.no_kernel_events:
+    if rank == 0 and args.full and not args.no_kernel_events:
         tl = ToolsLib(entry.build_tools())
         th = tl.context(n, dev.index)
 
@@ -750,9 +761,10 @@ def main():
     # forward + inverse leaves the batch unchanged: an end-to-end check of the timed region over EVERY transform (a skipped
     # or duplicated tile anywhere shows up here), plus -- a round trip is the identity for many wrong transforms too -- one
     # forward transform (the last of the batch) against the oracle, outside the timed region
-    assert torch.equal(data, check_before), "round trip changed the data"
+    if args.full:
+        assert torch.equal(data, check_before), "round trip changed the data"
     del check_before
-    if rank == 0 and args.log_n <= 22:
+    if rank == 0 and args.full and args.log_n <= 22:
         import oracle
         last = data[(batch - 1) * n:].clone()
         ctx.run_device(last.data_ptr(), last.data_ptr(), 1, False, stream=stream)
@@ -791,10 +803,11 @@ def main():
             },
             "gpu_event_ms_per_step": gpu_s / args.steps * 1e3,
             "ranks": ranks_table,
+            "roofline": None,
         }
 
     # ---- roofline of the dominant kernel: per-pass launch durations, HIP events on the launch stream ----
-    if rank == 0:
+    if rank == 0 and args.full:
         npass = ctx.passes_for(batch)
         if region is not None:
             fwd_ms, inv_ms = region["forward"], region["inverse"]
@@ -828,7 +841,7 @@ def main():
         }
 
     # ---- side measurements (not `value`) ----
-    if rank == 0 and not args.no_extras and world == 1:  # side measurements only on the single-GPU run
+    if rank == 0 and args.full and not args.no_extras and world == 1:  # side measurements only on the single-GPU run
         extras = {}
 
         def time_dev(fn, reps):
@@ -1341,7 +1354,7 @@ def main():
             "fri_fold_frac_of_hbm_peak": extras.get("fri_fold_m2^27", {}).get("frac_of_hbm_peak"),
         }
 
-    if rank == 0 and not args.no_cpu_baseline and world == 1:
+    if rank == 0 and args.full and not args.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args.log_n, args.cpu_seconds)
     elif rank == 0:
         out["cpu_baseline"] = None

@@ -67,7 +67,7 @@ def test_two_ranks_on_one_gpu_rehearsal():
     env["TOYNI_BENCH_BACKEND"] = "gloo"
     for extra in (["--batch", "8"], ["--workload", "slab", "--log-n", "22"], ["--workload", "fourstep", "--log-n", "20"]):
         res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                              "--no-extras", "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+                              "--full", "--no-extras", "--no-cpu-baseline"] + extra, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
         assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
         out = _last_json(res.stdout)
         assert out["n_gpus"] == 2 and out["rccl_ranks"] == 2 and out["value"] > 0
@@ -94,7 +94,8 @@ def test_single_process_slab_line_carries_roofline_and_baseline():
     """The configs[4] line as an 8-GPU node would print it, rehearsed with 8 lanes on the one device: `roofline` (algorithmic bytes vs
     the HBM of the devices in use, exchange bytes vs the xGMI links) and `cpu_baseline` (the oracle at n, or extrapolated and labelled)."""
     env = dict(os.environ, TOYNI_BENCH_LANES_ON_ONE_DEVICE="1")
-    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "slab-sp", "--gpus", "8", "--log-n", "25", "--steps", "2", "--warmup", "1"],
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "slab-sp", "--gpus", "8", "--log-n", "25", "--steps", "2", "--warmup", "1",
+                          "--full"],
                          capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     out = _last_json(res.stdout)
@@ -136,6 +137,34 @@ def test_dump_outputs_are_the_same_from_run_to_run(tmp_path):
     rt, fwd = dumps[0]["roundtrip.npy"], dumps[0]["forward.npy"]   # 8 transforms of 2^12: every one is dumped whole
     for i in range(8):
         assert (fwd[i].astype(np.uint64) == oracle.ntt(rt[i].astype(np.uint64))).all(), i
+
+
+@pytest.mark.gpu
+def test_plain_run_measures_value_only_and_full_adds_the_rest():
+    """A plain run prints the headline figure and nothing that takes work of its own; --full adds the checks and the roofline
+    object (kernel durations from the measurement build) to the same line."""
+    small = ["--log-n", "12", "--batch", "8", "--steps", "3", "--warmup", "1"]
+    lines = {}
+    for mode in ("plain", "full"):
+        res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + small + (["--full", "--no-extras", "--no-cpu-baseline"] if mode == "full" else []),
+                             capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        lines[mode] = _last_json(res.stdout)
+    for out in lines.values():
+        assert out["metric"] == "BabyBear NTT throughput (forward+inverse, device-resident)" and out["unit"] == "elements/s"
+        assert out["higher_is_better"] is True and out["dtype"] == "u32" and out["steps"] == 3 and out["warmup"] == 1
+        assert out["value"] > 0 and out["ms_per_step"] > 0 and out["value"] == pytest.approx(2 * 8 * 3 * (1 << 12) / (out["ms_per_step"] * 3e-3))
+    plain, full = lines["plain"], lines["full"]
+    assert plain["roofline"] is None and plain["cpu_baseline"] is None and "extras" not in plain
+    roof = full["roofline"]
+    assert roof["kernel_ms"] > 0 and "HIP events" in roof["kernel_ms_source"] and len(roof["all_pass_ms"]["forward"]) == full["config"]["passes_per_transform"]
+    # the one-transform workloads: the exchange check and the per-phase times are --full's as well
+    env = dict(os.environ, TOYNI_BENCH_LANES_ON_ONE_DEVICE="1")
+    res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "slab-sp", "--gpus", "8", "--log-n", "25", "--steps", "2", "--warmup", "1"],
+                         capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    out = _last_json(res.stdout)
+    assert out["value"] > 0 and out["exchange_verified"] is None and out["roofline"] is None and out["cpu_baseline"] is None
 
 
 def test_cpu_baseline_binary_is_built_outside_the_tree():

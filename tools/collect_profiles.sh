@@ -13,10 +13,10 @@ SUFFIX=""
 OUT=gpurun_out/profiles_$TAG$SUFFIX
 mkdir -p $OUT
 python3 tools/csrc_hash.py > $OUT/csrc_sha256.txt   # which kernels these profiles measure (bench.py checks it)
-CMD="python3 bench.py --steps 3 --warmup 1 --log-n $LOGN --batch $BATCH --no-extras --no-cpu-baseline"
+CMD="python3 bench.py --steps 3 --warmup 1 --log-n $LOGN --batch $BATCH --full --no-extras --no-cpu-baseline"
 # the timing pass runs bench.py's DEFAULT step counts (the command the bench line is judged on): averages over 20 steps, not over a
 # handful of launches that are still warming up; the counter passes replay kernels and keep the short run
-STATS_CMD="python3 bench.py --log-n $LOGN --batch $BATCH --no-extras --no-cpu-baseline"
+STATS_CMD="python3 bench.py --log-n $LOGN --batch $BATCH --full --no-extras --no-cpu-baseline"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $STATS_CMD > $OUT/stats.log 2>&1 || exit 1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -- $CMD > $OUT/fetch.log 2>&1 || exit 1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -- $CMD > $OUT/write.log 2>&1 || exit 1
