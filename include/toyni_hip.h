@@ -16,8 +16,10 @@
  *   4 bytes  every packed-u32 pointer not listed below: the transforms (plain, coset, Ext, LDE, Ext LDE), domain points, the
  *            four-step twiddle, the slab pass, the structured and explicit-point folds and the fold loop (16-byte aligned layers of
  *            whole quads take 16-byte accesses, others word accesses), the fold round's d_evals / d_out, the commit phase's
- *            d_layer0 / d_layers, quotient, DEEP, polynomial evaluation and its d_out, the openings' d_values / d_indices
- *   8 bytes  u64 pointers (toyni_ntt_device_u64, the narrow / widen pair) and the openings' d_out
+ *            d_layer0 / d_layers, quotient, DEEP, polynomial evaluation and its d_out, the openings' d_values / d_indices; the row commitment's and
+ *            row openings' d_values / d_indices (checked: TOYNI_E_RANGE below 4 bytes; a 16-byte aligned row-major matrix whose width
+ *            is a multiple of 4 takes 16-byte loads, others word loads)
+ *   8 bytes  u64 pointers (toyni_ntt_device_u64, the narrow / widen pair) and the openings' d_out (row openings included)
  *   16 bytes the Ext folds' d_evals / d_out (one 16-byte access per Ext element; d_xs needs 4), the slab relayout's and the fused
  *            slab rows' d_in / d_out, every Merkle d_levels / d_salts, the ChaCha20 fill's d_out
  *
@@ -265,6 +267,41 @@ int toyni_fri_fold_ext_host(uint64_t* h_out, const uint64_t* h_evals, size_t len
 size_t toyni_merkle_total_digests(size_t n);
 int toyni_merkle_commit_device(const uint32_t* d_values, const uint8_t* d_salts, size_t n, uint8_t* d_levels, void* stream);
 int toyni_merkle_commit_host(const uint64_t* h_values, const uint8_t* h_salts, size_t n, uint8_t* h_levels);
+
+/* ------------------------------------------------------------------------------------------------
+ * 3d. Merkle commitment whose leaf is one ROW of an n x width matrix of field elements, and the openings of such rows: a trace of
+ *     `width` columns under ONE tree, one authentication path per query.  Byte for byte MerkleTree::new (src/merkle.rs:16-48,
+ *     108-114) over
+ *         leaf_i = [salt_i (16 bytes)] || v(i,0).to_bytes() || ... || v(i,width-1).to_bytes()
+ *     (to_bytes = 8 LE bytes of the canonical residue, src/babybear.rs:53-55; salt first as in build_merkle_tree, absent when the
+ *     salts pointer is NULL).  width = 1 is the leaf of 3b: the same bytes as toyni_merkle_commit_device.  Two layouts:
+ *       TOYNI_ROWS_COLUMN_MAJOR  element (i, c) at d_values[c * col_stride + i], col_stride >= n: what the batched transforms and
+ *                                toyni_lde_device(batch = width) write (col_stride = n), committed as it lies -- no transpose.  The
+ *                                words between n and col_stride of a column are never read.
+ *       TOYNI_ROWS_ROW_MAJOR     element (i, c) at d_values[i * width + c] (col_stride ignored): an Ext vector (AoS) is width 4,
+ *                                its leaf Ext::to_bytes (src/ext.rs:83-89).  16-byte loads when width is a multiple of 4 and d_values
+ *                                is 16-byte aligned, word loads otherwise; same result.
+ *     d_levels: the layout of toyni_merkle_commit_device (toyni_merkle_total_digests(n) digests, leaf hashes first, root last).
+ *     Refused with TOYNI_E_RANGE before anything is enqueued: width == 0 or > 65536, an unknown layout, col_stride < n (column-major),
+ *     d_levels / d_salts not 16-byte aligned, d_values / d_indices not 4-byte aligned, d_out not 8-byte aligned.  n == 0 succeeds and
+ *     writes nothing.  A leaf costs ceil((8 width + 16 salted + 10) / 64) compressions.
+ * ---------------------------------------------------------------------------------------------- */
+#define TOYNI_ROWS_COLUMN_MAJOR 0
+#define TOYNI_ROWS_ROW_MAJOR 1
+size_t toyni_merkle_row_leaf_bytes(size_t width, int salted);          /* 16 * salted + 8 * width */
+int toyni_merkle_commit_rows_device(const uint32_t* d_values, size_t n, size_t width, int layout, size_t col_stride,
+                                    const uint8_t* d_salts, uint8_t* d_levels, void* stream);
+/* Host-slice form: h_values row-major n x width u64 elements, reduced mod p like BabyBear::new; h_salts n x 16 bytes or NULL;
+ * h_levels toyni_merkle_total_digests(n) x 32 bytes out.  Blocking. */
+int toyni_merkle_commit_rows_host(const uint64_t* h_values, size_t n, size_t width, const uint8_t* h_salts, uint8_t* h_levels);
+/* Openings of nidx rows, gathered on the device into nidx records of toyni_merkle_open_rows_record_bytes(n, width) bytes each:
+ * depth x 32 path bytes | 16 salt bytes (zero if d_salts is NULL) | width x 8 value bytes in leaf order | depth position bytes
+ * (1 = the sibling is the LEFT input), padding zero to a multiple of 8.  Every byte of a record is written.  For width = 1 this is
+ * the record of toyni_merkle_open_device.  The indices are device data: each < n is the caller's contract. */
+size_t toyni_merkle_open_rows_record_bytes(size_t n, size_t width);
+int toyni_merkle_open_rows_device(const uint8_t* d_levels, size_t n, const uint32_t* d_values, size_t width, int layout,
+                                  size_t col_stride, const uint8_t* d_salts, const uint32_t* d_indices, size_t nidx,
+                                  uint8_t* d_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:

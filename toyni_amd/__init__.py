@@ -13,7 +13,8 @@ from .ntt import (  # noqa: F401
 )
 from .fri import fri_fold, fri_fold_device, fri_fold_ext, fri_fold_ext_device, fri_fold_layers_device, fri_fold_xs_device  # noqa: F401
 from .domain import BabyBearDomain  # noqa: F401
-from .merkle import MerkleTree, merkle_commit_device  # noqa: F401
+from .merkle import (MerkleTree, RowMerkleTree, ROWS_COLUMN_MAJOR, ROWS_ROW_MAJOR, merkle_commit_device,  # noqa: F401
+                     merkle_commit_rows_device, merkle_open_rows_device)
 from . import prover  # noqa: F401
 
 P = 2013265921

@@ -104,6 +104,12 @@ SIGNATURES = {
     "toyni_merkle_total_digests": (c_size, [c_size]),
     "toyni_merkle_commit_device": (c_int, [c_void_p, c_void_p, c_size, c_void_p, c_void_p]),
     "toyni_merkle_commit_host": (c_int, [c_void_p, c_void_p, c_size, c_void_p]),
+    # section 3d
+    "toyni_merkle_row_leaf_bytes": (c_size, [c_size, c_int]),
+    "toyni_merkle_commit_rows_device": (c_int, [c_void_p, c_size, c_size, c_int, c_size, c_void_p, c_void_p, c_void_p]),
+    "toyni_merkle_commit_rows_host": (c_int, [c_void_p, c_size, c_size, c_void_p, c_void_p]),
+    "toyni_merkle_open_rows_record_bytes": (c_size, [c_size, c_size]),
+    "toyni_merkle_open_rows_device": (c_int, [c_void_p, c_size, c_void_p, c_size, c_int, c_size, c_void_p, c_void_p, c_size, c_void_p, c_void_p]),
     # section 3c
     "toyni_fri_fold_commit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

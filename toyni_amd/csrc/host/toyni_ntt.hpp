@@ -179,4 +179,22 @@ inline std::vector<BabyBear> fri_fold(const std::vector<BabyBear>& evals, const 
     return out;
 }
 
+// MerkleTree::new (src/merkle.rs:16-48) over the rows of a matrix, leaf = [salt] || v(i,0).to_bytes() || ... (include/toyni_hip.h 3d).
+// Host form: `rows` row-major n x width, `salts` n x 16 bytes or empty; returns every level back to back (leaf hashes first, root last).
+inline std::vector<uint8_t> merkle_commit_rows(const std::vector<BabyBear>& rows, size_t width, const std::vector<uint8_t>& salts = {}) {
+    if (width == 0 || rows.size() % width) throw std::logic_error("matrix size must be a multiple of its width");
+    const size_t n = rows.size() / width;
+    if (!salts.empty() && salts.size() != 16 * n) throw std::logic_error("one 16-byte salt per row");
+    std::vector<uint8_t> levels(32 * toyni_merkle_total_digests(n));
+    int st = toyni_merkle_commit_rows_host(reinterpret_cast<const uint64_t*>(rows.data()), n, width, salts.empty() ? nullptr : salts.data(), levels.data());
+    if (st != 0) throw std::runtime_error(std::string("GPU Merkle row commit failed: ") + toyni_error_string(st));
+    return levels;
+}
+// Device form: a packed-u32 matrix where the transforms left it (TOYNI_ROWS_COLUMN_MAJOR, col_stride = n after toyni_lde_device).
+inline Result merkle_commit_rows_device(const uint32_t* d_values, size_t n, size_t width, int layout, size_t col_stride, const uint8_t* d_salts,
+                                        uint8_t* d_levels, void* stream) {
+    int st = toyni_merkle_commit_rows_device(d_values, n, width, layout, col_stride, d_salts, d_levels, stream);
+    return st == 0 ? Result{} : Result{std::string("GPU Merkle row commit failed: ") + toyni_error_string(st)};
+}
+
 }  // namespace toyni

@@ -112,6 +112,106 @@ TOYNI_HD Digest merkle_leaf(uint32_t value, const uint32_t* salt_words /* 4 LE w
     return digest_of(st);
 }
 
+// ---- leaf of one ROW of an n x width matrix (include/toyni_hip.h 3d) --------------------------------------------------------
+// MerkleTree::new over leaf = [salt (16)] || v_0.to_bytes() || ... || v_{width-1}.to_bytes()  (src/merkle.rs:16-48,108-114; the
+// salt first as build_merkle_tree has it, src/fibonacci.rs:340-353).  The message 00 || leaf is L = 1 + 16 salted + 8 width bytes,
+// ceil((L + 9) / 64) blocks.  A value is v0 v1 v2 v3 00 00 00 00 and the tag shifts everything by one byte, so with vb = bswap(v) a
+// value is exactly the TWO message words (vb >> 8, vb << 24) -- the upper four bytes are never loaded or shuffled -- and a block is
+// EIGHT value slots.  Unsalted, block b holds columns 8b .. 8b + 7.  Salted, the salt takes slots 0 and 1 of block 0 (plus the top
+// byte of slot 2: s15), which moves every later column two slots on: block b holds columns 8b - 2 .. 8b + 5.
+// Values arrive in CHUNKS of eight columns 8j .. 8j + 7 (load(j, v): whatever lies at or beyond `width` is ignored), so a loader can
+// use aligned 16-byte accesses whatever the salt does; the salted form carries the last two words of a chunk into the next block.
+// The slot that follows the last column holds the padding byte (00 80 00 00); if that is slot 7 the length needs a block of its
+// own (L mod 64 = 57).  Chunk b + 1 is requested BEFORE the 64 rounds of block b.  The block loop is rolled (its trip count is data);
+// everything inside it indexes registers with constants.
+TOYNI_HD void row_slot_words(uint32_t value, int col, int width, uint32_t& w_even, uint32_t& w_odd) {
+    const uint32_t vb = sha_bswap(value);
+    w_even = col < width ? vb >> 8 : (col == width ? 0x00800000u : 0u);
+    w_odd = col < width ? vb << 24 : 0u;
+}
+template <bool SALTED, class LoadChunk>
+TOYNI_HD Digest merkle_row_leaf(uint32_t width, const uint32_t* salt_words /* 4 LE words when SALTED */, LoadChunk&& load) {
+    const int wd = (int)width;
+    const int nwords = 2 * wd + (SALTED ? 4 : 0);      // message words that hold data; the padding byte sits in word `nwords`
+    const int nblocks = (nwords + 3 + 15) / 16;        // + padding word + 64-bit length
+    const int nchunks = (wd + 7) / 8;
+    Sha256State st = sha256_init();
+    uint32_t nxt[8], carry[2] = {0u, 0u};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) nxt[k] = 0u;
+    load(0, nxt);
+    for (int b = 0; b < nblocks; ++b) {
+        uint32_t v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) { v[k] = nxt[k]; nxt[k] = 0u; }
+        if (b + 1 < nchunks) load(b + 1, nxt);          // in flight across this block's rounds
+        uint32_t w[16];
+        if (SALTED) {
+            row_slot_words(carry[0], 8 * b - 2, wd, w[0], w[1]);
+            row_slot_words(carry[1], 8 * b - 1, wd, w[2], w[3]);
+#pragma unroll
+            for (int k = 2; k < 8; ++k) row_slot_words(v[k - 2], 8 * b - 2 + k, wd, w[2 * k], w[2 * k + 1]);
+            carry[0] = v[6];
+            carry[1] = v[7];
+            if (b == 0) {
+                uint32_t s[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) s[j] = sha_bswap(salt_words[j]);  // big-endian view of salt bytes 4j..4j+3
+                w[0] = s[0] >> 8;                       // 00 s0 s1 s2
+                w[1] = (s[0] << 24) | (s[1] >> 8);
+                w[2] = (s[1] << 24) | (s[2] >> 8);
+                w[3] = (s[2] << 24) | (s[3] >> 8);
+                w[4] |= s[3] << 24;                     // s15 v0 v1 v2
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) row_slot_words(v[k], 8 * b + k, wd, w[2 * k], w[2 * k + 1]);
+        }
+        if (b == nblocks - 1) w[15] = 8u * (1u + 4u * (uint32_t)nwords);   // bits of 00 || leaf (width <= 65536: one word)
+        sha256_compress(st, w);
+    }
+    return digest_of(st);
+}
+
+// The chunk loaders of the two layouts (values of include/toyni_hip.h's TOYNI_ROWS_*), for row i:
+//   column-major: element (i, c) at values[c * col_stride + i] -- one word from each of 8 columns; the 64 lanes of a wave read 256
+//                 consecutive bytes of each column
+//   row-major   : element (i, c) at values[i * width + c] -- 8 consecutive words of the row: two 16-byte loads when `vec` (width a
+//                 multiple of 4, so a quad is inside the row or outside it, and the matrix 16-byte aligned), else word loads
+// Only columns below `width` are addressed: nothing between n and col_stride, nothing past the matrix.
+constexpr int ROWS_COLUMN_MAJOR = 0, ROWS_ROW_MAJOR = 1;
+struct alignas(16) RowQuad { uint32_t x, y, z, w; };
+template <int LAYOUT>
+TOYNI_HD void rows_load_chunk(const uint32_t* values, uint64_t i, uint32_t width, uint64_t col_stride, bool vec, int j, uint32_t (&v)[8]) {
+    const uint32_t c0 = 8u * (uint32_t)j;
+    if (LAYOUT == ROWS_COLUMN_MAJOR) {
+        const uint32_t* p = values + (uint64_t)c0 * col_stride + i;
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k)
+            if (c0 + k < width) v[k] = p[(uint64_t)k * col_stride];
+    } else {
+        const uint32_t* p = values + i * (uint64_t)width + c0;
+        if (vec) {
+            const RowQuad a = *reinterpret_cast<const RowQuad*>(p);
+            v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+            if (c0 + 4 < width) {
+                const RowQuad b = *reinterpret_cast<const RowQuad*>(p + 4);
+                v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+            }
+        } else {
+#pragma unroll
+            for (uint32_t k = 0; k < 8; ++k)
+                if (c0 + k < width) v[k] = p[k];
+        }
+    }
+}
+// the leaf of row i of a matrix in memory: what the leaf kernels run per thread, and what tests/emu steps on the CPU
+template <int LAYOUT, bool SALTED>
+TOYNI_HD Digest merkle_row_leaf_at(const uint32_t* values, uint64_t i, uint32_t width, uint64_t col_stride, bool vec, const uint32_t* salt_words) {
+    return merkle_row_leaf<SALTED>(width, salt_words,
+                                   [=](int j, uint32_t (&v)[8]) { rows_load_chunk<LAYOUT>(values, i, width, col_stride, vec, j, v); });
+}
+
 // node = SHA256(01 || left || right): 65 bytes, two blocks
 TOYNI_HD Digest merkle_node(const Digest& left, const Digest& right) {
     uint32_t d[16];  // big-endian words of left || right

@@ -744,6 +744,52 @@ __device__ __forceinline__ void merkle_open_group(const OpenGroup& g, uint64_t f
 __global__ void __launch_bounds__(256) merkle_open_kernel(const OpenGroup g) {
     merkle_open_group(g, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, (uint64_t)gridDim.x * blockDim.x);
 }
+// Openings of row leaves (include/toyni_hip.h 3d): per opening, one thread per level copies the sibling digest and writes the position
+// byte, one writes salt and padding, one per column writes that value's 8 bytes.  Record: depth x 32 | salt 16 | width x 8 | depth
+// position bytes, zero-padded to a multiple of 8 -- merkle_open_kernel's record when width = 1.
+struct OpenRows {
+    const Digest* levels;
+    uint64_t n;
+    const uint32_t* values;
+    uint32_t width;
+    int layout;
+    uint64_t col_stride;
+    const uint4* salts;
+    const uint32_t* indices;
+    uint32_t nidx;
+    uint8_t* out;
+};
+__global__ void __launch_bounds__(256) merkle_open_rows_kernel(const OpenRows g) {
+    const uint32_t depth = merkle_depth(g.n);
+    const uint64_t values_at = (uint64_t)depth * 32u + 16u, flags_at = values_at + 8u * (uint64_t)g.width;
+    const uint64_t rec = flags_at + ((depth + 7u) & ~7u);
+    const uint64_t per = (uint64_t)depth + 1u + g.width, total = (uint64_t)g.nidx * per;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < total; w += stride) {
+        const uint32_t k = (uint32_t)(w / per);
+        const uint64_t item = w % per;
+        const uint64_t index = g.indices[k];
+        uint8_t* r = g.out + (uint64_t)k * rec;
+        if (item < depth) {
+            bool is_left;
+            const uint64_t row = merkle_sibling_row(g.n, index, (uint32_t)item, is_left);
+            reinterpret_cast<Digest*>(r)[item] = g.levels[row];        // records are 8-byte aligned, digests are u32 words
+            r[flags_at + item] = is_left ? 1 : 0;
+        } else if (item == depth) {
+            uint32_t* tail = reinterpret_cast<uint32_t*>(r + (uint64_t)depth * 32u);
+            uint4 sv = make_uint4(0u, 0u, 0u, 0u);
+            if (g.salts) sv = g.salts[index];
+            tail[0] = sv.x; tail[1] = sv.y; tail[2] = sv.z; tail[3] = sv.w;
+            for (uint64_t b = flags_at + depth; b < rec; ++b) r[b] = 0;   // byte stores, clear of the position bytes
+        } else {
+            const uint64_t c = item - depth - 1u;
+            uint32_t* val = reinterpret_cast<uint32_t*>(r + values_at + 8u * c);
+            val[0] = g.layout == TOYNI_ROWS_COLUMN_MAJOR ? g.values[c * g.col_stride + index] : g.values[index * g.width + c];
+            val[1] = 0u;
+        }
+    }
+}
+
 // every tree of a proof in ONE launch (blockIdx.y = tree): the 19 launches of a 2^16-row proof's query phase were ~5 us each
 constexpr uint32_t OPEN_GROUPS_MAX = 32;
 struct OpenGroups { OpenGroup g[OPEN_GROUPS_MAX]; };
@@ -936,6 +982,25 @@ __global__ void __launch_bounds__(256) merkle_leaf_kernel(const uint32_t* __rest
         out[i] = d;
     }
 }
+// Leaf hashes of the ROWS of an n x width matrix (merkle_row_leaf_at, merkle_kernels.hpp): one thread per row, the launch shape of
+// merkle_leaf_kernel.  LAYOUT x SALTED = four instantiations and no more: whether a row-major matrix takes 16-byte loads is a
+// uniform run-time flag (`vec`), not a third parameter.  Row-major lanes are `width` words apart: correct for every width, meant
+// for narrow rows (an Ext vector is width 4).
+static_assert(ROWS_COLUMN_MAJOR == TOYNI_ROWS_COLUMN_MAJOR && ROWS_ROW_MAJOR == TOYNI_ROWS_ROW_MAJOR, "layout codes of the header");
+template <int LAYOUT, bool SALTED>
+__global__ void __launch_bounds__(256) merkle_rows_leaf_kernel(const uint32_t* __restrict__ values, const uint4* __restrict__ salts,
+                                                                Digest* __restrict__ out, size_t n, uint32_t width, size_t col_stride, bool vec) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        uint32_t sw[4] = {0u, 0u, 0u, 0u};
+        if constexpr (SALTED) {
+            const uint4 s = salts[i];
+            sw[0] = s.x; sw[1] = s.y; sw[2] = s.z; sw[3] = s.w;
+        }
+        out[i] = merkle_row_leaf_at<LAYOUT, SALTED>(values, i, width, col_stride, vec, sw);
+    }
+}
+
 // One thread per node: the levels large enough to fill the chip.  (Round 3 also tried block 2's schedule from the SHA_B2 table here --
 // 480 instructions fewer per hash, 64 gathers more: 246 against 253 us for the 2^20-leaf FRI round, nothing on a whole proof; not kept.)
 __global__ void __launch_bounds__(256) merkle_level_kernel(const Digest* __restrict__ cur, Digest* __restrict__ next, size_t m, size_t up) {
@@ -2600,6 +2665,84 @@ int toyni_merkle_commit_host(const uint64_t* h_values, const uint8_t* h_salts, s
     HIPCHK(hipMemcpyAsync(h_levels, st->buf[4], total * 32, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     return TOYNI_OK;
+}
+
+// ---- row leaves of a multi-column matrix (include/toyni_hip.h 3d) ----
+constexpr size_t MERKLE_ROWS_MAX_WIDTH = 65536;
+size_t toyni_merkle_row_leaf_bytes(size_t width, int salted) { return (salted ? 16u : 0u) + 8u * width; }
+
+static int rows_args_check(size_t n, size_t width, int layout, size_t col_stride) {
+    if (width == 0 || width > MERKLE_ROWS_MAX_WIDTH) return TOYNI_E_RANGE;
+    if (layout != TOYNI_ROWS_COLUMN_MAJOR && layout != TOYNI_ROWS_ROW_MAJOR) return TOYNI_E_RANGE;
+    if (layout == TOYNI_ROWS_COLUMN_MAJOR && col_stride < n) return TOYNI_E_RANGE;
+    return TOYNI_OK;
+}
+
+int toyni_merkle_commit_rows_device(const uint32_t* d_values, size_t n, size_t width, int layout, size_t col_stride, const uint8_t* d_salts,
+                                    uint8_t* d_levels, void* stream) {
+    if (!d_values || !d_levels) return TOYNI_E_NULL;
+    if (int rc = rows_args_check(n, width, layout, col_stride)) return rc;
+    if (((uintptr_t)d_levels & 15) || ((uintptr_t)d_salts & 15) || ((uintptr_t)d_values & 3)) return TOYNI_E_RANGE;
+    if (n == 0) return TOYNI_OK;
+    hipStream_t s = (hipStream_t)stream;
+    const uint4* salts = reinterpret_cast<const uint4*>(d_salts);
+    Digest* out = reinterpret_cast<Digest*>(d_levels);
+    const uint32_t w = (uint32_t)width;
+    const bool vec = layout == TOYNI_ROWS_ROW_MAJOR && width % 4 == 0 && !((uintptr_t)d_values & 15);
+    const dim3 grid(grid_for(n)), block(256);
+    if (layout == TOYNI_ROWS_COLUMN_MAJOR) {
+        if (salts) hipLaunchKernelGGL((merkle_rows_leaf_kernel<TOYNI_ROWS_COLUMN_MAJOR, true>), grid, block, 0, s, d_values, salts, out, n, w, col_stride, vec);
+        else hipLaunchKernelGGL((merkle_rows_leaf_kernel<TOYNI_ROWS_COLUMN_MAJOR, false>), grid, block, 0, s, d_values, salts, out, n, w, col_stride, vec);
+    } else {
+        if (salts) hipLaunchKernelGGL((merkle_rows_leaf_kernel<TOYNI_ROWS_ROW_MAJOR, true>), grid, block, 0, s, d_values, salts, out, n, w, col_stride, vec);
+        else hipLaunchKernelGGL((merkle_rows_leaf_kernel<TOYNI_ROWS_ROW_MAJOR, false>), grid, block, 0, s, d_values, salts, out, n, w, col_stride, vec);
+    }
+    return enqueue_merkle_upper(d_levels, n, s);
+}
+
+int toyni_merkle_commit_rows_host(const uint64_t* h_values, size_t n, size_t width, const uint8_t* h_salts, uint8_t* h_levels) {
+    if (!h_values || !h_levels) return TOYNI_E_NULL;
+    if (int rc = rows_args_check(n, width, TOYNI_ROWS_ROW_MAJOR, 0)) return rc;
+    if (n == 0) return TOYNI_OK;
+    HostStage* st = nullptr;
+    int dev = 0, rc;
+    if ((rc = host_stage_acquire(&st, &dev))) return rc;
+    std::lock_guard<std::mutex> lk(st->mu);
+    hipStream_t s = st->stream;
+    const size_t total = toyni_merkle_total_digests(n), elems = n * width;
+    // slots: 0 = values u64, 1 = salts, 2 = values u32, 4 = all levels
+    if ((rc = host_stage_reserve(st, 0, elems * sizeof(uint64_t)))) return rc;
+    if (h_salts && (rc = host_stage_reserve(st, 1, n * 16))) return rc;
+    if ((rc = host_stage_reserve(st, 2, elems * sizeof(uint32_t)))) return rc;
+    if ((rc = host_stage_reserve(st, 4, total * 32))) return rc;
+    HIPCHK(hipMemcpyAsync(st->buf[0], h_values, elems * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+    if (h_salts) HIPCHK(hipMemcpyAsync(st->buf[1], h_salts, n * 16, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(narrow_kernel, dim3(grid_for(elems)), dim3(256), 0, s, (const uint64_t*)st->buf[0], (uint32_t*)st->buf[2], elems);
+    if ((rc = toyni_merkle_commit_rows_device((const uint32_t*)st->buf[2], n, width, TOYNI_ROWS_ROW_MAJOR, 0, h_salts ? (const uint8_t*)st->buf[1] : nullptr,
+                                              (uint8_t*)st->buf[4], s))) return rc;
+    HIPCHK(hipMemcpyAsync(h_levels, st->buf[4], total * 32, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return TOYNI_OK;
+}
+
+size_t toyni_merkle_open_rows_record_bytes(size_t n, size_t width) {
+    if (n == 0) return 0;
+    const size_t d = merkle_depth(n);
+    return d * 32u + 16u + 8u * width + ((d + 7u) & ~(size_t)7u);
+}
+
+int toyni_merkle_open_rows_device(const uint8_t* d_levels, size_t n, const uint32_t* d_values, size_t width, int layout, size_t col_stride,
+                                  const uint8_t* d_salts, const uint32_t* d_indices, size_t nidx, uint8_t* d_out, void* stream) {
+    if (!d_levels || !d_values || !d_indices || !d_out) return TOYNI_E_NULL;
+    if (int rc = rows_args_check(n, width, layout, col_stride)) return rc;
+    if (n > 0xFFFFFFFFull || nidx > 0xFFFFFFFFull || ((uintptr_t)d_levels & 15) || ((uintptr_t)d_salts & 15) || ((uintptr_t)d_out & 7) ||
+        ((uintptr_t)d_values & 3) || ((uintptr_t)d_indices & 3)) return TOYNI_E_RANGE;
+    if (n == 0 || nidx == 0) return TOYNI_OK;
+    const uint64_t work = (uint64_t)nidx * (merkle_depth(n) + 1 + width);
+    const OpenRows g{reinterpret_cast<const Digest*>(d_levels), (uint64_t)n, d_values, (uint32_t)width, layout, (uint64_t)col_stride,
+                     reinterpret_cast<const uint4*>(d_salts), d_indices, (uint32_t)nidx, d_out};
+    hipLaunchKernelGGL(merkle_open_rows_kernel, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream, g);
+    return (int)hipGetLastError();
 }
 
 // ---- fold + commit, pointwise prover steps (include/toyni_hip.h 3c) ----

@@ -60,3 +60,50 @@ class MerkleTree:
 def merkle_commit_device(d_values: int, d_salts: int, n: int, d_levels: int, stream: int = 0) -> None:
     """Device-resident form: packed u32 values, optional 16-byte salts, all levels written to d_levels."""
     check(lib.toyni_merkle_commit_device(d_values, d_salts or None, n, d_levels, stream or None), "GPU Merkle commit failed")
+
+
+ROWS_COLUMN_MAJOR = 0   # TOYNI_ROWS_COLUMN_MAJOR: element (i, c) at values[c * col_stride + i]
+ROWS_ROW_MAJOR = 1      # TOYNI_ROWS_ROW_MAJOR:    element (i, c) at values[i * width + c]
+
+
+class RowMerkleTree(MerkleTree):
+    """Tree whose leaf is one ROW of an (n, width) matrix: [salt(16)] || v(i,0) (8, LE) || ... || v(i,width-1) (8, LE).
+    MerkleTree::new (src/merkle.rs:16-48) over such leaves; width = 1 is MerkleTree.  u64 inputs are reduced mod p like
+    BabyBear::new."""
+
+    def __init__(self, matrix, salts=None):
+        m = np.ascontiguousarray(matrix, dtype=np.uint64)
+        assert m.ndim == 2 and m.shape[0] > 0 and m.shape[1] > 0, "an (n, width) matrix"
+        n, width = m.shape
+        s = None
+        if salts is not None:
+            s = np.ascontiguousarray(salts, dtype=np.uint8).reshape(n, 16)
+        flat = np.empty((lib.toyni_merkle_total_digests(n), 32), dtype=np.uint8)
+        check(lib.toyni_merkle_commit_rows_host(m.ctypes.data, n, width, s.ctypes.data if s is not None else None, flat.ctypes.data),
+              "GPU Merkle row commit failed")
+        self.n, self.width = n, width
+        self._values = m % np.uint64(2013265921)
+        self._salts = s
+        self.levels, off = [], 0
+        for k in level_sizes(n):
+            self.levels.append(flat[off:off + k])
+            off += k
+
+    def leaf_bytes(self, index: int) -> bytes:
+        """The leaf the tree hashed for row `index` (what verify_merkle_proof, src/merkle.rs:87-101, is given)."""
+        salt = self._salts[index].tobytes() if self._salts is not None else b""
+        return salt + self._values[index].astype("<u8").tobytes()
+
+
+def merkle_commit_rows_device(d_values: int, n: int, width: int, layout: int, col_stride: int, d_salts: int, d_levels: int,
+                              stream: int = 0) -> None:
+    """Device-resident row commitment: packed u32 matrix in either layout, optional 16-byte salts, all levels to d_levels."""
+    check(lib.toyni_merkle_commit_rows_device(d_values, n, width, layout, col_stride, d_salts or None, d_levels, stream or None),
+          "GPU Merkle row commit failed")
+
+
+def merkle_open_rows_device(d_levels: int, n: int, d_values: int, width: int, layout: int, col_stride: int, d_salts: int,
+                            d_indices: int, nidx: int, d_out: int, stream: int = 0) -> None:
+    """nidx opening records of toyni_merkle_open_rows_record_bytes(n, width) bytes each, gathered on the device into d_out."""
+    check(lib.toyni_merkle_open_rows_device(d_levels, n, d_values, width, layout, col_stride, d_salts or None, d_indices, nidx, d_out,
+                                            stream or None), "GPU Merkle row opening failed")
