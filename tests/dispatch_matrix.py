@@ -50,11 +50,11 @@ class Dev:
 
 def batches_for(log_n, cap_log_elems):
     """Batches that select the different tile widths of an n-point plan: a lone transform and three (latency shapes / narrow tiles),
-    then enough transforms for 2^7, 2^9 and 2^12 32-wide tiles (the thresholds of ntt_plan.hpp) of the plan's smallest and of its
-    largest pass."""
+    then enough transforms for 2^7, 2^9 and 2^12 32-wide tiles (the thresholds of ntt_plan.hpp) of every pass of the plan: both
+    passes of a two-pass split, all three of a three-pass one (split_passes: the sizes c <= b <= a of n >= 2^21, up to 2^27)."""
     out = [1, 3]
     if log_n >= 11:
-        ms = {log_n // 2, (log_n + 1) // 2} if log_n <= 20 else {log_n // 3, (log_n + 2) // 3}
+        ms = {log_n // 2, (log_n + 1) // 2} if log_n <= 20 else {log_n // 3, (log_n + 1) // 3, (log_n + 2) // 3}
         for m in ms:
             for lt in (7, 9, 12):
                 b = 1 << max(0, lt + 5 + m - log_n)

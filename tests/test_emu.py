@@ -42,6 +42,39 @@ def test_kernel_bodies_match_oracle_on_cpu():
     assert m and int(m.group(2)) > 0 and int(m.group(3)) > 0, "both the two-step and the three-step shapes must have run"
 
 
+def _run_emu_cases(exe, cases, workers, timeout):
+    """Each case (a list of emulator arguments after the leading `0`: no default size loop) as its own process, `workers` at a time,
+    the slowest first -- the wall time stays near the slowest case."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    def run(args):
+        res = subprocess.run([exe, "0"] + args, capture_output=True, text=True, timeout=timeout)
+        ok = res.returncode == 0 and "ALL OK" in res.stdout
+        return None if ok else " ".join(args) + ":\n" + res.stdout[-2000:] + res.stderr[-2000:]
+
+    with ThreadPoolExecutor(max_workers=workers) as ex:
+        failed = [r for r in ex.map(run, cases) if r]
+    assert not failed, "\n".join(failed)
+
+
+def test_three_pass_plans_of_2_23_to_2_26_on_cpu():
+    """The plans the GPU suite reaches in tests/test_gpu_three_pass.py, stepped on the CPU: splits (7,8,8), (8,8,9) and (8,9,9) --
+    plain, coset and LDE by 32 and 4 (a bare size), Ext vectors at 2^23, and the zero-aware first pass across zero fractions: 128
+    points at 2^23 (blow-ups 2, 8, 32 and 128 = the whole first pass; a blow-up of 256 is the launcher's pad-and-transform, which
+    has no kernel of its own to step), 256 points at 2^25 and 2^26.  2^23 again on the 64-wide shapes alone (w0) and with the
+    three-step shapes off (p-1).
+    Wall time: 236 s on 8 CPUs, four single-threaded processes at a time (641 s of CPU time in all; `26`, the slowest case,
+    sets the floor)."""
+    exe = entry.build_emu()
+    _run_emu_cases(exe, [["26"], ["25"], ["e23"], ["l26x5"], ["l25x4"], ["23"], ["w0", "23"], ["p-1", "23"],
+                         ["l23x1"], ["l23x3"], ["l23x5"], ["l23x7"]], workers=4, timeout=1800)
+
+
+def test_three_pass_plan_of_2_23_is_memory_safe_under_asan_ubsan():
+    # the (7,8,8) split, plain / coset / LDE by 32 and 4, under the sanitizers: 36 s for `23` and 12 s for `l23x5`, side by side
+    _run_emu_cases(entry.build_emu_sanitized(), [["23"], ["l23x5"]], workers=2, timeout=900)
+
+
 def test_kernel_bodies_are_memory_safe_under_asan_ubsan():
     # every tile / LDS / table index of every pass shape stays in bounds (global buffers are exactly n * batch words,
     # the LDS array exactly LDS_WORDS): 2^0..2^11 with ragged batches (2^11 also through the single-sweep LDS kernel in all its

@@ -430,9 +430,11 @@ def test_full_size_2_27_roundtrip(ta):
 
 @pytest.mark.parametrize("log_n,vecs", [(24, 2), (27, 1)])
 def test_full_size_ext_vectors(ta, log_n, vecs):
-    """The interleaved (Ext, AoS) passes at the sizes no oracle run can afford: element offsets reach 2^29 words at n = 2^27 (the
-    limit of the 32-bit tile-relative byte offsets).  Every coordinate against the single-device BASE transform of that coordinate
-    (itself pinned at these sizes by the tests above), direct DFT spot checks, and the round trip."""
+    """The interleaved (Ext, AoS) passes at the largest sizes: element offsets reach 2^29 words at n = 2^27 (the limit of the 32-bit
+    tile-relative byte offsets).  Every coordinate against the single-device BASE transform of that coordinate (itself compared with
+    the oracle output for output at these sizes: 2^24 above, 2^27 and every other three-pass size in tests/test_gpu_three_pass.py --
+    an oracle transform of 2^24 points takes about 6 s on one thread, of 2^27 about a minute), direct DFT spot checks, the round
+    trip, and at 2^24 one coordinate column against the oracle itself."""
     n = 1 << log_n
     rng = np.random.default_rng(2700 + log_n)
     x = rng.integers(0, P, size=(vecs, n, 4), dtype=np.uint32)
@@ -452,6 +454,9 @@ def test_full_size_ext_vectors(ta, log_n, vecs):
         for k in range(4):
             col = np.ascontiguousarray(x[v, :, k])
             assert (y[v, :, k] == dev_transform(ta, col, n, 1, False)).all(), (v, k)
+    if log_n == 24:
+        v, k = vecs - 1, 2
+        assert (y[v, :, k] == oracle.ntt(x[v, :, k].astype(np.uint64))).all(), "coordinate column against the oracle"
     _spot_check_dft(np.ascontiguousarray(x[vecs - 1, :, 3]), np.ascontiguousarray(y[vecs - 1, :, 3]), n, [0, 1, 4097, n // 2, n - 1])
 
 
