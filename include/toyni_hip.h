@@ -304,6 +304,44 @@ int toyni_merkle_open_rows_device(const uint8_t* d_levels, size_t n, const uint3
                                   uint8_t* d_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * 3e. Between "committed" and "folded" for a trace of several columns: the out-of-domain values of every column in one call, and the
+ *     DEEP codeword of any set of (column, rotation) terms over a column-major matrix -- the general form of toyni_poly_eval_device
+ *     and toyni_fib_deep_device (3c), inside the same protocol shape: z and the weights are base-field elements (squeeze_challenge,
+ *     src/transcript.rs:34-40) and there is one common denominator x - z (src/fibonacci.rs:193-196).  With 3d the sequence
+ *         batched inverse transform -> toyni_lde_device(batch = w) -> toyni_merkle_commit_rows_device -> toyni_poly_eval_batch_device
+ *         -> toyni_deep_combine_device -> toyni_fri_commit_phase_device -> toyni_merkle_open_rows_device
+ *     stays on the device; only the AIR's own constraint evaluation is the caller's.
+ *     Both calls are asynchronous on `stream`, take packed-u32 canonical residues and write canonical residues.  Device pointers are
+ *     4-byte aligned.  `points` and `terms` are host arrays that the caller may reuse as soon as the call returns.  Both calls may use the
+ *     context's per-stream intermediate buffer (calls on one stream run in order; use one stream per concurrent call).
+ *     Refused before anything is enqueued -- TOYNI_E_NULL for a null context or pointer; TOYNI_E_RANGE for: npoints outside 1..4; a
+ *     point, z, alpha or value >= p; shift == 0 or >= p; log_blowup > log2 N; stride < ncoeffs with batch > 1; batch >= 2^32; col_stride < N;
+ *     width == 0 or > 65536; column >= width; rotation >= N / B; nterms > 2^20; a device pointer that is not 4-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+/* d_out[b * npoints + p] = sum_i d_coeffs[b * stride + i] * points[p]^i,  i < ncoeffs,  b < batch,  1 <= npoints <= 4: every column
+ * equals toyni_poly_eval_device on that column.  Two launches for the whole batch.  ncoeffs == 0 writes batch x npoints zeros (the
+ * zero polynomial); batch == 0 succeeds and writes nothing. */
+int toyni_poly_eval_batch_device(toyni_ntt_ctx* ctx, const uint32_t* d_coeffs, size_t ncoeffs, size_t stride, size_t batch,
+                                 const uint32_t* points, unsigned npoints, uint32_t* d_out, void* stream);
+typedef struct { uint32_t column, rotation, alpha, value; } toyni_deep_term;
+/* With N = the context's n, B = 1 << log_blowup, x_i = shift * w_N^i, M(c, i) = d_values[c * col_stride + i] (the column-major layout
+ * of 3d; the words between N and col_stride of a column are never read):
+ *   d_i = ( sum_t alpha_t * (M(column_t, (i + rotation_t * B) mod N) - value_t) ) / (x_i - z)
+ * i.e. term t is the column's polynomial at g^rotation_t x, g = w_(N/B), against its claimed value at g^rotation_t z.
+ * accumulate != 0: d_out[i] = d_out[i] + d_i, so a second matrix (the quotient's, say) is a second call.  The Fibonacci layer of
+ * toyni_fib_deep_device is the four terms (0,0,1,t_z) (0,1,1,t_gz) (0,2,1,t_ggz) (1,0,1,q_z), word for word.  Terms may repeat and
+ * come in any order.  A point with x_i = z yields 0 for that point alone (with accumulate: adds 0), the rule of
+ * toyni_fib_deep_device.  nterms == 0 writes N zeros, or leaves d_out alone when accumulating.  d_out must not overlap the matrix.
+ * The matrix is read by 16-byte loads where the column's first word is 16-byte aligned and rotation * B is a multiple of 4 (N >= 8),
+ * by word loads otherwise; the result is the same.  Up to 64 terms travel inside the kernel's arguments.  A longer table is copied
+ * from a pinned staging ring of the context into its per-stream buffer by a stream-ordered copy (the call stays asynchronous; when
+ * the ring wraps, once per 64 KiB of tables at the least, the call first waits for the stream): with more than 64 terms the call
+ * cannot be captured into a HIP graph. */
+int toyni_deep_combine_device(toyni_ntt_ctx* ctx, const uint32_t* d_values, size_t width, size_t col_stride, unsigned log_blowup,
+                              uint32_t shift, uint32_t z, const toyni_deep_term* terms, size_t nterms, int accumulate,
+                              uint32_t* d_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:
  *     src/fibonacci.rs:133-150,186-198,222-245, src/math/polynomial.rs:134-144, src/merkle.rs:50-80).  All asynchronous on
  *     `stream`; packed u32 device data; ctx = a context of size N = the LDE size (its domain table supplies x_i = shift w_N^i).

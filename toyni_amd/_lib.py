@@ -110,6 +110,9 @@ SIGNATURES = {
     "toyni_merkle_commit_rows_host": (c_int, [c_void_p, c_size, c_size, c_void_p, c_void_p]),
     "toyni_merkle_open_rows_record_bytes": (c_size, [c_size, c_size]),
     "toyni_merkle_open_rows_device": (c_int, [c_void_p, c_size, c_void_p, c_size, c_int, c_size, c_void_p, c_void_p, c_size, c_void_p, c_void_p]),
+    # section 3e
+    "toyni_poly_eval_batch_device": (c_int, [c_void_p, c_void_p, c_size, c_size, c_size, c_void_p, ctypes.c_uint, c_void_p, c_void_p]),
+    "toyni_deep_combine_device": (c_int, [c_void_p, c_void_p, c_size, c_size, ctypes.c_uint, c_u32, c_u32, c_void_p, c_size, c_int, c_void_p, c_void_p]),
     # section 3c
     "toyni_fri_fold_commit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

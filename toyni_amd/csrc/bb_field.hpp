@@ -136,6 +136,16 @@ TOYNI_HD uint32_t mont_dot2(uint32_t a, uint32_t bR, uint32_t c, uint32_t dR) {
     t += (uint64_t)m * BB_P;
     return bb_reduce_2p((uint32_t)(t >> 32));
 }
+// Montgomery reduction of a sum of up to FOUR products of canonical factors (t < 4 p^2 < 2^64): t / R mod p, canonical.
+// t + m p would pass 2^64, so the high word (< 4 p^2 / 2^32 < 1.88 p) first drops one p -- a multiple of p R leaves the sum,
+// the low word and with it m are untouched -- and then hi' 2^32 + lo + m p < 2 p 2^32 < 2^64 with a quotient below 2p.
+// Four products then cost 4 multiply-adds + 6 operations where four mont_mul + three bb_add cost 29.
+TOYNI_HD uint32_t mont_reduce_wide(uint64_t t) {
+    const uint32_t lo = (uint32_t)t, hi = bb_reduce_2p((uint32_t)(t >> 32));
+    const uint32_t m = lo * BB_NPINV;
+    const uint64_t u = (((uint64_t)hi << 32) | lo) + (uint64_t)m * BB_P;
+    return bb_reduce_2p((uint32_t)(u >> 32));
+}
 // aR^(p-2) in the Montgomery domain (a R -> a^-1 R; 0 -> 0), BabyBear::inverse (src/babybear.rs:111-114) by an addition chain:
 // p - 2 = 0b111_0_(27 ones) = 15 * 2^27 - 1 is built as 0b1110 followed by nine times "shift by three, append 0b111":
 // 30 squarings + 11 products = 41 Montgomery products where the square-and-multiply ladder spends 30 + 30.

@@ -99,6 +99,113 @@ TOYNI_HD void deep_group(const DeepArgs& a, uint64_t i0, const uint32_t (&t0)[K]
     }
 }
 
+// ---- DEEP combination of a column-major matrix (include/toyni_hip.h 3e): the layer above for any set of columns ----
+//   d_i = ( sum_t alpha_t M(column_t, (i + rot_t) mod N) - C ) / (x_i - z),   C = sum_t alpha_t value_t  (host, once)
+// One table entry per term, sorted by (column, rot) on the host so that the rotations of a column are read back to back.
+struct alignas(16) DeepTerm {
+    uint32_t column;
+    uint32_t rot;            // rotation * B: the distance in words, < N
+    uint32_t alphaR;         // Montgomery form of the weight
+    uint32_t pad;
+};
+struct DeepCombineArgs {
+    const uint32_t* values;  // element (i, c) at values[c * col_stride + i]
+    uint32_t* out;
+    uint64_t col_stride;
+    DomainArgs dom;
+    uint32_t log_N, nterms;
+    uint32_t wNR;            // Montgomery form of w_N
+    uint32_t zR;             // Montgomery form of z
+    uint32_t claim;          // C, plain
+    uint32_t accumulate;
+};
+typedef uint32_t DeepQuad __attribute__((vector_size(16)));   // one 16-byte load as a whole (a struct of four words is split and re-merged unevenly)
+// the K words of one term for the points i0 .. i0 + K - 1 (i0 a multiple of K; N a multiple of K): two 16-byte loads where the
+// column's first word is 16-byte aligned and the rotation a multiple of 4 (each quad then lies inside the column: N is a multiple
+// of 8, so only a whole quad wraps), word loads otherwise
+template <int K>
+TOYNI_HD void deep_term_load(const DeepCombineArgs& a, const DeepTerm& t, uint64_t i0, uint32_t (&v)[K]) {
+    const uint64_t mask = ((uint64_t)1 << a.log_N) - 1;
+    const uint32_t* col = a.values + (uint64_t)t.column * a.col_stride;
+    if (K == 8 && !(((uintptr_t)col & 15) | (t.rot & 3u))) {
+        const DeepQuad lo = *reinterpret_cast<const DeepQuad*>(col + ((i0 + t.rot) & mask));
+        const DeepQuad hi = *reinterpret_cast<const DeepQuad*>(col + ((i0 + t.rot + 4) & mask));
+        const uint32_t w[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+#pragma unroll
+        for (int j = 0; j < K; ++j) v[j] = w[j & 7];
+    } else {
+#pragma unroll
+        for (int j = 0; j < K; ++j) v[j] = col[(i0 + (uint64_t)j + t.rot) & mask];
+    }
+}
+// (x_j - z)^-1 R for the K points from i0 on, by ONE Fermat inversion (Montgomery's trick, as deep_group); 0 where x_j = z
+template <int K>
+TOYNI_HD void deep_point_inverses(const DomainArgs& dom, uint32_t wNR, uint32_t zR, uint64_t i0, uint32_t (&invR)[K]) {
+    uint32_t dR[K], pre[K];
+    uint32_t xR = domain_point_mont(dom, i0);
+    uint32_t acc = BB_R1;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        dR[j] = bb_sub(xR, zR);
+        if (dR[j] == 0u) dR[j] = BB_R1 | 0x80000000u;   // marker (never a canonical value)
+        pre[j] = acc;
+        acc = mont_mul(acc, (dR[j] & 0x80000000u) ? BB_R1 : dR[j]);
+        if (j + 1 < K) xR = mont_mul(xR, wNR);
+    }
+    uint32_t inv = mont_inv(acc);
+#pragma unroll
+    for (int j = K - 1; j >= 0; --j) {
+        const bool zero = (dR[j] & 0x80000000u) != 0u;
+        invR[j] = zero ? 0u : mont_mul(inv, pre[j]);
+        if (!zero) inv = mont_mul(inv, dR[j]);
+    }
+}
+// entry t of the table: the same in every lane, so scalar registers and uniform branches
+TOYNI_HD DeepTerm deep_term_at(const DeepTerm* terms, uint32_t t) {
+    return DeepTerm{TOYNI_UNIFORM(terms[t].column), TOYNI_UNIFORM(terms[t].rot), TOYNI_UNIFORM(terms[t].alphaR), 0u};
+}
+// The products of four terms share one Montgomery reduction (mont_reduce_wide): 4 multiply-adds + 9 operations per point, 3.25 per
+// term, where one mont_mul + bb_add per term spends 8 and pairs through mont_dot2 spend 4.5.  The term loop's trip count is data;
+// everything inside it indexes registers with constants.
+template <int K>
+TOYNI_HD void deep_combine_group(const DeepCombineArgs& a, const DeepTerm* terms, uint64_t i0, uint32_t (&d)[K]) {
+    uint32_t sum[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) sum[j] = 0u;
+    uint32_t t = 0;
+    for (; t + 4 <= a.nterms; t += 4) {
+        uint64_t acc[K];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const DeepTerm tm = deep_term_at(terms, t + q);
+            uint32_t v[K];
+            deep_term_load<K>(a, tm, i0, v);
+#pragma unroll
+            for (int j = 0; j < K; ++j) acc[j] = (q ? acc[j] : 0ull) + (uint64_t)v[j] * tm.alphaR;
+        }
+#pragma unroll
+        for (int j = 0; j < K; ++j) sum[j] = bb_add(sum[j], mont_reduce_wide(acc[j]));
+    }
+    if (t < a.nterms) {   // one to three terms left
+        uint64_t acc[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) acc[j] = 0ull;
+        for (; t < a.nterms; ++t) {
+            const DeepTerm tm = deep_term_at(terms, t);
+            uint32_t v[K];
+            deep_term_load<K>(a, tm, i0, v);
+#pragma unroll
+            for (int j = 0; j < K; ++j) acc[j] += (uint64_t)v[j] * tm.alphaR;
+        }
+#pragma unroll
+        for (int j = 0; j < K; ++j) sum[j] = bb_add(sum[j], mont_reduce_wide(acc[j]));
+    }
+    uint32_t invR[K];
+    deep_point_inverses<K>(a.dom, a.wNR, a.zR, i0, invR);
+#pragma unroll
+    for (int j = 0; j < K; ++j) d[j] = mont_mul(bb_sub(sum[j], a.claim), invR[j]);
+}
+
 // ---- polynomial evaluation at up to POLY_MAX_POINTS points ----
 constexpr int POLY_MAX_POINTS = 4;
 constexpr uint32_t POLY_PER_THREAD = 16, POLY_THREADS = 256, POLY_CHUNK = POLY_PER_THREAD * POLY_THREADS;
@@ -119,6 +226,30 @@ TOYNI_HD uint32_t poly_thread_term(const PolyEvalArgs& a, uint32_t p, const uint
 #pragma unroll
     for (int j = (int)POLY_PER_THREAD - 2; j >= 0; --j) r = bb_add(mont_mul(r, a.zR[p]), c[j]);
     return mont_mul(r, mont_pow(a.z16R[p], t));
+}
+
+// The same for `batch` coefficient vectors `stride` words apart (include/toyni_hip.h 3e): stage 1 runs one block per (chunk, column),
+// stage 2 one block per column.  e.coeffs is column 0, e.partial holds [column][chunk][point], e.out holds [column][point].
+struct PolyBatchArgs {
+    PolyEvalArgs e;
+    uint64_t stride;
+    uint32_t batch;
+};
+TOYNI_HD void poly_batch_load(const PolyBatchArgs& a, uint32_t col, uint32_t chunk, uint32_t t, uint32_t (&c)[POLY_PER_THREAD]) {
+    const uint32_t* src = a.e.coeffs + (uint64_t)col * a.stride;
+    const uint64_t base = (uint64_t)chunk * POLY_CHUNK + (uint64_t)t * POLY_PER_THREAD;
+#pragma unroll
+    for (uint32_t j = 0; j < POLY_PER_THREAD; ++j) c[j] = base + j < a.e.ncoeffs ? src[base + j] : 0u;
+}
+TOYNI_HD uint64_t poly_batch_partial_index(const PolyBatchArgs& a, uint32_t col, uint32_t chunk, uint32_t p) {
+    return ((uint64_t)col * a.e.nblocks + chunk) * a.e.npoints + p;
+}
+// stage 2, thread t of nthreads: its share of sum_chunk partial[col][chunk][p] * (z^POLY_CHUNK)^chunk
+TOYNI_HD uint32_t poly_batch_final_thread(const PolyBatchArgs& a, uint32_t col, uint32_t p, uint32_t t, uint32_t nthreads) {
+    uint32_t acc = 0;
+    for (uint32_t b = t; b < a.e.nblocks; b += nthreads)
+        acc = bb_add(acc, mont_mul(a.e.partial[poly_batch_partial_index(a, col, b, p)], mont_pow(a.e.zchunkR[p], b)));
+    return acc;
 }
 
 // ---- Merkle openings (src/merkle.rs:50-80, src/fibonacci.rs:366-375) ----

@@ -705,6 +705,66 @@ __global__ void __launch_bounds__(256) poly_eval_final_kernel(const PolyEvalArgs
     }
 }
 
+// the batched form: grid (chunk, column) -- columns beyond the grid's y extent are taken in further rounds
+__global__ void __launch_bounds__(256) poly_eval_batch_partial_kernel(const PolyBatchArgs a) {
+    __shared__ uint32_t red[256];
+    for (uint32_t col = blockIdx.y; col < a.batch; col += gridDim.y) {
+        uint32_t c[POLY_PER_THREAD];
+        poly_batch_load(a, col, blockIdx.x, threadIdx.x, c);
+        for (uint32_t p = 0; p < a.e.npoints; ++p) {
+            const uint32_t sum = block_sum_mod(poly_thread_term(a.e, p, c, threadIdx.x), red);
+            if (threadIdx.x == 0) a.e.partial[poly_batch_partial_index(a, col, blockIdx.x, p)] = sum;
+        }
+    }
+}
+// one block per column
+__global__ void __launch_bounds__(256) poly_eval_batch_final_kernel(const PolyBatchArgs a) {
+    __shared__ uint32_t red[256];
+    for (uint32_t col = blockIdx.x; col < a.batch; col += gridDim.x)
+        for (uint32_t p = 0; p < a.e.npoints; ++p) {
+            const uint32_t sum = block_sum_mod(poly_batch_final_thread(a, col, p, threadIdx.x, blockDim.x), red);
+            if (threadIdx.x == 0) a.e.out[(uint64_t)col * a.e.npoints + p] = sum;
+        }
+}
+
+// DEEP combination of a column-major matrix: one group of 8 consecutive points per thread (no grid-stride loop: every read of
+// the term table then precedes the thread's only stores, so the table is fetched by scalar loads); single points below N = 8
+__device__ __forceinline__ void deep_combine_body(const DeepCombineArgs& a, const DeepTerm* terms) {
+    constexpr int K = 8;
+    const uint64_t N = (uint64_t)1 << a.log_N;
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a.log_N >= 3) {
+        if (g >= N / K) return;
+        const uint64_t i0 = g * K;
+        uint32_t d[K];
+        deep_combine_group<K>(a, terms, i0, d);
+        uint4* o = reinterpret_cast<uint4*>(a.out + i0);
+        if (!((uintptr_t)a.out & 15)) {
+            if (a.accumulate) {
+                const uint4 p0 = o[0], p1 = o[1];
+                const uint32_t prev[K] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+#pragma unroll
+                for (int j = 0; j < K; ++j) d[j] = bb_add(prev[j], d[j]);
+            }
+            o[0] = make_uint4(d[0], d[1], d[2], d[3]);
+            o[1] = make_uint4(d[4], d[5], d[6], d[7]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < K; ++j) a.out[i0 + j] = a.accumulate ? bb_add(a.out[i0 + j], d[j]) : d[j];
+        }
+    } else if (g < N) {
+        uint32_t d[1];
+        deep_combine_group<1>(a, terms, g, d);
+        a.out[g] = a.accumulate ? bb_add(a.out[g], d[0]) : d[0];
+    }
+}
+// the table in device memory (any length) ...
+__global__ void __launch_bounds__(256) deep_combine_kernel(const DeepCombineArgs a, const DeepTerm* __restrict__ terms) { deep_combine_body(a, terms); }
+// ... or, up to DEEP_INLINE_TERMS entries, inside the kernel arguments: no copy ahead of the launch, and the call can be captured
+constexpr uint32_t DEEP_INLINE_TERMS = 64;
+struct DeepInlineTerms { DeepTerm t[DEEP_INLINE_TERMS]; };
+__global__ void __launch_bounds__(256) deep_combine_inline_kernel(const DeepCombineArgs a, const DeepInlineTerms in) { deep_combine_body(a, in.t); }
+
 // Merkle openings: one thread per (opening, level) copies the sibling digest; one thread per opening adds salt, value, flags
 struct OpenGroup {
     const Digest* levels;
@@ -1141,6 +1201,8 @@ struct toyni_ntt_ctx {
         size_t stage64_elems = 0;
         uint32_t* d_lde32 = nullptr;     // compact coefficient vectors of the LDE entry points
         size_t lde32_words = 0;
+        uint8_t* h_ring = nullptr;       // pinned staging ring: host tables that a stream-ordered copy reads after the call returned
+        size_t ring_bytes = 0, ring_head = 0;
         uint64_t tick = 0;               // last use (eviction order)
         hipEvent_t fence = nullptr;      // recorded on the set's stream at the end of the last call that used it (when `fenced`)
         bool fenced = false;             // `fence` covers every use of the set so far
@@ -1243,6 +1305,7 @@ void retire_scratch(toyni_ntt_ctx* c, toyni_ntt_ctx::Scratch& sc, hipStream_t s,
     for (void* p : {(void*)sc.d_work, (void*)sc.d_data32, (void*)sc.d_stage64, (void*)sc.d_lde32})
         if (p) { c->retired.push_back({p, s, stream_known, ev, false}); handed = true; }
     if (sc.fence && !(ev && handed)) (void)hipEventDestroy(sc.fence);
+    if (sc.h_ring) (void)hipHostFree(sc.h_ring);   // waits for the copies that still read it (eviction, trim, destroy: never the steady state)
     sc = toyni_ntt_ctx::Scratch();
 }
 
@@ -1271,6 +1334,25 @@ int grow(toyni_ntt_ctx* c, hipStream_t s, void** buf, size_t* have, size_t need,
     if (*buf) { c->retired.push_back({*buf, s, true, nullptr, true}); *buf = nullptr; *have = 0; }   // fresh: finish_call fences it on s
     HIPCHK(hipMalloc(buf, need * elem_bytes));
     *have = need;
+    return 0;
+}
+
+// `bytes` of the set's pinned staging ring.  Slices are handed out in order; before the ring wraps or is replaced by a larger one the
+// stream is drained, so no slice is rewritten while an enqueued copy may still read it (once per 64 KiB of tables at the least).
+int ring_slice(toyni_ntt_ctx::Scratch& sc, hipStream_t s, size_t bytes, void** out) {
+    bytes = (bytes + 63) & ~(size_t)63;
+    if (sc.ring_head + bytes > sc.ring_bytes) {
+        HIPCHK(hipStreamSynchronize(s));
+        sc.ring_head = 0;
+        if (bytes > sc.ring_bytes) {
+            if (sc.h_ring) { (void)hipHostFree(sc.h_ring); sc.h_ring = nullptr; sc.ring_bytes = 0; }
+            const size_t want = std::max<size_t>(bytes, (size_t)64 << 10);
+            HIPCHK(hipHostMalloc((void**)&sc.h_ring, want, hipHostMallocDefault));
+            sc.ring_bytes = want;
+        }
+    }
+    *out = sc.h_ring + sc.ring_head;
+    sc.ring_head += bytes;
     return 0;
 }
 
@@ -2935,6 +3017,96 @@ int toyni_poly_eval_device(toyni_ntt_ctx* c, const uint32_t* d_coeffs, size_t nc
     }
     hipLaunchKernelGGL(poly_eval_partial_kernel, dim3(a.nblocks), dim3(POLY_THREADS), 0, s, a);
     hipLaunchKernelGGL(poly_eval_final_kernel, dim3(1), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+// ---- section 3e: the out-of-domain values of a whole batch, and the DEEP combination of a column-major matrix ----
+int toyni_poly_eval_batch_device(toyni_ntt_ctx* c, const uint32_t* d_coeffs, size_t ncoeffs, size_t stride, size_t batch, const uint32_t* points,
+                                 unsigned npoints, uint32_t* d_out, void* stream) {
+    if (!c || !points || !d_out || (!d_coeffs && ncoeffs)) return TOYNI_E_NULL;
+    if (npoints < 1 || npoints > (unsigned)POLY_MAX_POINTS) return TOYNI_E_RANGE;
+    for (unsigned p = 0; p < npoints; ++p) if (points[p] >= BB_P) return TOYNI_E_RANGE;
+    if ((batch > 1 && stride < ncoeffs) || batch > 0xFFFFFFFFull || (((uintptr_t)d_coeffs | (uintptr_t)d_out) & 3)) return TOYNI_E_RANGE;
+    if (batch == 0) return TOYNI_OK;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (ncoeffs == 0) return (int)hipMemsetAsync(d_out, 0, batch * npoints * sizeof(uint32_t), s);   // zero polynomials
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    PolyBatchArgs a{};
+    a.e.coeffs = d_coeffs;
+    a.e.ncoeffs = ncoeffs;
+    a.e.npoints = npoints;
+    a.e.nblocks = (uint32_t)((ncoeffs + POLY_CHUNK - 1) / POLY_CHUNK);
+    a.stride = stride;
+    a.batch = (uint32_t)batch;
+    int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words, batch * a.e.nblocks * npoints, sizeof(uint32_t));
+    if (rc) return rc;
+    a.e.partial = sc.d_lde32;
+    a.e.out = d_out;
+    for (unsigned p = 0; p < npoints; ++p) {
+        a.e.zR[p] = to_mont_host(points[p]);
+        a.e.z16R[p] = to_mont_host(bb_pow_host(points[p], POLY_PER_THREAD));
+        a.e.zchunkR[p] = to_mont_host(bb_pow_host(points[p], POLY_CHUNK));
+    }
+    const unsigned rows = (unsigned)std::min<size_t>(batch, 65535);
+    hipLaunchKernelGGL(poly_eval_batch_partial_kernel, dim3(a.e.nblocks, rows), dim3(POLY_THREADS), 0, s, a);
+    hipLaunchKernelGGL(poly_eval_batch_final_kernel, dim3(rows), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+int toyni_deep_combine_device(toyni_ntt_ctx* c, const uint32_t* d_values, size_t width, size_t col_stride, unsigned log_blowup, uint32_t shift,
+                              uint32_t z, const toyni_deep_term* terms, size_t nterms, int accumulate, uint32_t* d_out, void* stream) {
+    if (!c || !d_values || !d_out || (!terms && nterms)) return TOYNI_E_NULL;
+    const int log_N = c->plan.log_n;
+    const uint64_t N = 1ull << log_N;
+    if ((int)log_blowup > log_N || shift == 0 || shift >= BB_P || z >= BB_P || width == 0 || width > 65536 || col_stride < N ||
+        nterms > ((size_t)1 << 20) || (((uintptr_t)d_values | (uintptr_t)d_out) & 3))
+        return TOYNI_E_RANGE;
+    for (size_t t = 0; t < nterms; ++t)
+        if (terms[t].column >= width || terms[t].rotation >= (N >> log_blowup) || terms[t].alpha >= BB_P || terms[t].value >= BB_P) return TOYNI_E_RANGE;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (nterms == 0) return accumulate ? TOYNI_OK : (int)hipMemsetAsync(d_out, 0, N * sizeof(uint32_t), s);
+    // the table the kernel reads: sorted by (column, rotation) so that the rotations of one column -- B words apart, lines the
+    // first of them has just fetched -- are read back to back; the claimed values collapse into one constant
+    std::vector<DeepTerm> table(nterms);
+    uint32_t claim = 0;
+    for (size_t t = 0; t < nterms; ++t) {
+        table[t] = DeepTerm{terms[t].column, (uint32_t)((uint64_t)terms[t].rotation << log_blowup), to_mont_host(terms[t].alpha), 0u};
+        claim = (uint32_t)((claim + (uint64_t)terms[t].alpha * terms[t].value) % BB_P);
+    }
+    std::stable_sort(table.begin(), table.end(), [](const DeepTerm& x, const DeepTerm& y) { return x.column != y.column ? x.column < y.column : x.rot < y.rot; });
+    DeepCombineArgs a{};
+    a.values = d_values;
+    a.out = d_out;
+    a.col_stride = col_stride;
+    a.dom = domain_args(c, (unsigned)log_N, shift);
+    a.log_N = (uint32_t)log_N;
+    a.nterms = (uint32_t)nterms;
+    a.wNR = to_mont_host(bb_root_of_unity_host((uint32_t)log_N));
+    a.zR = to_mont_host(z);
+    a.claim = claim;
+    a.accumulate = accumulate ? 1u : 0u;
+    const uint64_t items = log_N >= 3 ? N / 8 : N;
+    const dim3 grid((unsigned)((items + 255) / 256));
+    if (nterms <= DEEP_INLINE_TERMS) {   // the table rides in the kernel arguments
+        DeepInlineTerms in{};
+        std::copy(table.begin(), table.end(), in.t);
+        hipLaunchKernelGGL(deep_combine_inline_kernel, grid, dim3(256), 0, s, a, in);
+        return (int)hipGetLastError();
+    }
+    // a longer table: pinned staging ring -> the stream's intermediate buffer by a stream-ordered copy (an earlier call's kernel on
+    // this stream is ahead of the copy; the ring keeps the bytes alive until the copy has run)
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words, nterms * (sizeof(DeepTerm) / sizeof(uint32_t)), sizeof(uint32_t));
+    if (rc) return rc;
+    void* h = nullptr;
+    if ((rc = ring_slice(sc, s, nterms * sizeof(DeepTerm), &h))) return rc;
+    std::memcpy(h, table.data(), nterms * sizeof(DeepTerm));
+    HIPCHK(hipMemcpyAsync(sc.d_lde32, h, nterms * sizeof(DeepTerm), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(deep_combine_kernel, grid, dim3(256), 0, s, a, reinterpret_cast<const DeepTerm*>(sc.d_lde32));
     return (int)hipGetLastError();
 }
 

@@ -63,6 +63,34 @@ def poly_eval_device(ctx, d_coeffs: int, ncoeffs: int, points, d_out: int, strea
     check(lib.toyni_poly_eval_device(ctx.handle, d_coeffs, ncoeffs, p.ctypes.data, p.size, d_out, stream or None), "GPU polynomial evaluation failed")
 
 
+def poly_eval_batch_device(ctx, d_coeffs: int, ncoeffs: int, stride: int, batch: int, points, d_out: int, stream: int = 0) -> None:
+    """d_out[b * npoints + p] = column b (d_coeffs + b * stride words) evaluated at points[p]: the out-of-domain values of a whole
+    trace in two launches (include/toyni_hip.h 3e)."""
+    p = np.ascontiguousarray(points, dtype=np.uint32)
+    check(lib.toyni_poly_eval_batch_device(ctx.handle, d_coeffs or None, ncoeffs, stride, batch, p.ctypes.data, p.size, d_out, stream or None),
+          "GPU batched polynomial evaluation failed")
+
+
+class DeepTerm(ctypes.Structure):   # toyni_deep_term (include/toyni_hip.h 3e)
+    _fields_ = [("column", ctypes.c_uint32), ("rotation", ctypes.c_uint32), ("alpha", ctypes.c_uint32), ("value", ctypes.c_uint32)]
+
+
+def deep_terms(columns, rotations, alphas, values):
+    """The term table of deep_combine_device: term t weighs column columns[t], read rotations[t] trace rows ahead, by alphas[t]
+    against the claimed value values[t]."""
+    cols, rots, als, vals = (np.asarray(v, dtype=np.uint32).ravel() for v in (columns, rotations, alphas, values))
+    assert cols.size == rots.size == als.size == vals.size
+    return (DeepTerm * cols.size)(*[DeepTerm(int(c), int(r), int(a), int(v)) for c, r, a, v in zip(cols, rots, als, vals)])
+
+
+def deep_combine_device(ctx, d_values: int, width: int, col_stride: int, log_blowup: int, shift: int, z: int, terms, d_out: int,
+                        accumulate: bool = False, stream: int = 0) -> None:
+    """d_out[i] (+)= sum_t alpha_t (M(column_t, i + rotation_t B) - value_t) / (x_i - z) over a column-major matrix on the LDE coset
+    (include/toyni_hip.h 3e).  terms: what deep_terms returns."""
+    check(lib.toyni_deep_combine_device(ctx.handle, d_values, width, col_stride, log_blowup, shift, z, terms if len(terms) else None, len(terms),
+                                        1 if accumulate else 0, d_out, stream or None), "GPU DEEP combination failed")
+
+
 def merkle_open_record_bytes(n: int) -> int:
     return lib.toyni_merkle_open_record_bytes(n)
 
