@@ -310,7 +310,7 @@ int toyni_merkle_open_rows_device(const uint8_t* d_levels, size_t n, const uint3
  *     src/transcript.rs:34-40) and there is one common denominator x - z (src/fibonacci.rs:193-196).  With 3d the sequence
  *         batched inverse transform -> toyni_lde_device(batch = w) -> toyni_merkle_commit_rows_device -> toyni_poly_eval_batch_device
  *         -> toyni_deep_combine_device -> toyni_fri_commit_phase_device -> toyni_merkle_open_rows_device
- *     stays on the device; only the AIR's own constraint evaluation is the caller's.
+ *     stays on the device; the AIR's constraint evaluation between the commitment and the quotient is 3f.
  *     Both calls are asynchronous on `stream`, take packed-u32 canonical residues and write canonical residues.  Device pointers are
  *     4-byte aligned.  `points` and `terms` are host arrays that the caller may reuse as soon as the call returns.  Both calls may use the
  *     context's per-stream intermediate buffer (calls on one stream run in order; use one stream per concurrent call).
@@ -340,6 +340,78 @@ typedef struct { uint32_t column, rotation, alpha, value; } toyni_deep_term;
 int toyni_deep_combine_device(toyni_ntt_ctx* ctx, const uint32_t* d_values, size_t width, size_t col_stride, unsigned log_blowup,
                               uint32_t shift, uint32_t z, const toyni_deep_term* terms, size_t nterms, int accumulate,
                               uint32_t* d_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 3f. The constraints of any AIR, evaluated into the quotient codeword: the step between toyni_merkle_commit_rows_device and the
+ *     quotient's own commitment that 3e left to the caller, and the general form of toyni_fib_quotient_device (3c).  A constraint
+ *     system is a small straight-line program over registers r[0 .. nregs), nregs <= TOYNI_AIR_MAX_REGS; every point of the LDE
+ *     coset runs it on a register file of its own.  With N = the context's n, B = 1 << log_blowup, n = N / B, x_i = shift * w_N^i,
+ *     g = w_n, M_m(c, i) = mats[m].d_values[c * mats[m].col_stride + i] (the column-major layout toyni_lde_device(batch = w) writes
+ *     and 3d / 3e read; the words between N and col_stride are never read), an instruction does at point i:
+ *         TOYNI_AIR_CELL    r[dst] = M_b(imm, (i + a * B) mod N)   matrix b < 4, rotation a, column imm: the column's polynomial at g^a x_i
+ *         TOYNI_AIR_CONST   r[dst] = imm                            imm < p
+ *         TOYNI_AIR_X       r[dst] = x_i
+ *         TOYNI_AIR_XINV    r[dst] = (x_i - imm)^-1                 imm < p; 0 where x_i = imm, the rule of toyni_deep_combine_device
+ *         TOYNI_AIR_ADD / _SUB / _MUL   r[dst] = r[a] o r[b]
+ *         TOYNI_AIR_EMIT    constraint number imm has the value r[a]; b = 0: it joins the numerator that is divided by
+ *                           Z_H(x) = x^n - 1; b = 1: it is added undivided (a boundary constraint already divided through XINV)
+ *     and a call with the weights of its Fiat-Shamir challenge (base-field elements, as in 3e) computes
+ *         c_i = sum_{EMIT k, b = 0} weights[k] * value_k(i)
+ *         q_i = c_i / (x_i^n - 1) + sum_{EMIT k, b = 1} weights[k] * value_k(i)
+ *     A constraint number may be emitted more than once; its values add.  Exact field arithmetic on canonical residues throughout.
+ *     The quotient of toyni_fib_quotient_device (src/fibonacci.rs:133-150) is the 13 instructions
+ *         CELL(0,0) CELL(0,1) CELL(0,2) ADD SUB X CONST(g^(n-1)) SUB MUL CONST(g^(n-2)) SUB MUL EMIT(0, b = 0)   with weights = {1},
+ *     word for word.
+ * ---------------------------------------------------------------------------------------------- */
+#define TOYNI_AIR_MAX_REGS 64
+#define TOYNI_AIR_MAX_MATRICES 4
+#define TOYNI_AIR_CELL 0
+#define TOYNI_AIR_CONST 1
+#define TOYNI_AIR_X 2
+#define TOYNI_AIR_XINV 3
+#define TOYNI_AIR_ADD 4
+#define TOYNI_AIR_SUB 5
+#define TOYNI_AIR_MUL 6
+#define TOYNI_AIR_EMIT 7
+typedef struct { uint8_t op, dst, a, b; uint32_t imm; } toyni_air_insn;
+typedef struct { const uint32_t* d_values; size_t width, col_stride; } toyni_air_matrix;
+/* What a call must supply: nregs = highest register + 1, nconstraints = highest EMIT number + 1, nmatrices = highest matrix + 1,
+ * min_width[m] = highest column of matrix m + 1 (0: the program does not read it), max_rotation, divides_by_zh = some EMIT has b = 0. */
+typedef struct { uint32_t ninsns, nregs, nconstraints, nmatrices, max_rotation, divides_by_zh;
+                 uint32_t min_width[TOYNI_AIR_MAX_MATRICES]; } toyni_air_info;
+typedef struct toyni_air_program toyni_air_program;
+/* Validation, on the host alone (no device, no context).  TOYNI_E_NULL for a null argument; TOYNI_E_RANGE for: ninsns == 0 or
+ * > 65536; an unknown op; a dst, a or b register >= 64; a register read before any instruction wrote it (the program is a straight
+ * line: one scan); CONST or XINV with imm >= p; CELL with matrix >= 4 or column >= 65536; EMIT with imm >= 65536 or b > 1; no EMIT.
+ * The register rules bind the fields an op uses as registers: dst of every op but EMIT, a and b of ADD / SUB / MUL, a of EMIT.  CELL's
+ * a and b are a rotation and a matrix, EMIT's b is the flag.  The fields an op does not use (a and b of CONST / X / XINV, imm of X and
+ * of ADD / SUB / MUL, dst of EMIT) are ignored and not checked: write 0 there. */
+int toyni_air_program_check(const toyni_air_insn* insns, size_t ninsns, toyni_air_info* info);
+/* The same check, then the program in the device's form (constants in Montgomery form) uploaded to ctx's device; blocking.  The
+ * program serves every context on that device, any number of calls and streams at a time.  toyni_air_program_destroy is null-safe
+ * and waits for the device first. */
+int toyni_air_program_create(toyni_ntt_ctx* ctx, const toyni_air_insn* insns, size_t ninsns, toyni_air_program** out);
+int toyni_air_program_destroy(toyni_air_program* prog);
+int toyni_air_program_info(const toyni_air_program* prog, toyni_air_info* info);
+/* Runs the program at every point of the coset and writes q (and c, unless d_c_out is NULL).  Asynchronous on `stream`; packed-u32
+ * canonical residues in and out; `mats` and `weights` are host arrays that the caller may reuse as soon as the call returns.
+ * accumulate != 0: d_q_out[i] += q_i and d_c_out[i] += c_i.  Outputs must not overlap a matrix.
+ * Refused before anything is enqueued, the outputs untouched -- TOYNI_E_NULL for a null context, program, weights or d_q_out (or
+ * mats with nmats > 0); TOYNI_E_RANGE for: nmats < info.nmatrices or > 4; a matrix the program reads with a null d_values,
+ * width < min_width[m], width > 65536 or col_stride < N; max_rotation >= N / B; log_blowup > log2 N; shift == 0 or >= p;
+ * nweights < nconstraints or > 65536; a weight >= p; a device pointer that is not 4-byte aligned; a program created on another
+ * device.  TOYNI_E_ZERO_INVERSE, as toyni_fib_quotient_device, when divides_by_zh is set and Z_H vanishes on the coset.
+ * Cells are read by 16-byte loads where the column's first word is 16-byte aligned and rotation * B is a multiple of 4 (N >= 4), by
+ * word loads otherwise, and the outputs are written by 16-byte stores where they are 16-byte aligned; the result is the same.  The
+ * register file lives in LDS, nregs x 16 bytes per thread, in workgroups of the largest of 256 / 128 / 64 threads that keeps it within
+ * 64 KiB: a program that needs few registers runs at a higher occupancy.  1 / Z_H costs one inversion per residue class i mod B and
+ * workgroup where B <= 256 and the 4 B bytes fit behind the register file, one per four points otherwise.
+ * Up to 64 weights travel inside the kernel's arguments, and such a call can be captured into a HIP graph.  More are copied from the
+ * context's pinned staging ring into its per-stream buffer by a stream-ordered copy, as the term table of toyni_deep_combine_device
+ * (the call stays asynchronous; it cannot be captured). */
+int toyni_air_quotient_device(toyni_ntt_ctx* ctx, const toyni_air_program* prog, const toyni_air_matrix* mats, size_t nmats,
+                              unsigned log_blowup, uint32_t shift, const uint32_t* weights, size_t nweights, uint32_t* d_c_out,
+                              uint32_t* d_q_out, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:

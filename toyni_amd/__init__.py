@@ -16,5 +16,6 @@ from .domain import BabyBearDomain  # noqa: F401
 from .merkle import (MerkleTree, RowMerkleTree, ROWS_COLUMN_MAJOR, ROWS_ROW_MAJOR, merkle_commit_device,  # noqa: F401
                      merkle_commit_rows_device, merkle_open_rows_device)
 from . import prover  # noqa: F401
+from .prover import AirBuilder, AirProgram, air_insns, air_quotient_device  # noqa: F401  (include/toyni_hip.h 3f)
 
 P = 2013265921

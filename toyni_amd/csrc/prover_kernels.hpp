@@ -49,10 +49,11 @@ struct QuotientArgs {
     uint32_t wBR;            // Montgomery form of w_B = w_N^n
 };
 // 1 / Z_H(x_i) = 1 / (x_i^n - 1) for residue class t = i mod B, Montgomery form (one Fermat inversion per class, not per point)
-TOYNI_HD uint32_t quotient_zh_inv(const QuotientArgs& a, uint32_t t) {
-    const uint32_t xnR = mont_mul(a.shift_nR, mont_pow(a.wBR, t));   // (shift^n w_B^t) R
+TOYNI_HD uint32_t zh_inv_class(uint32_t shift_nR, uint32_t wBR, uint32_t t) {
+    const uint32_t xnR = mont_mul(shift_nR, mont_pow(wBR, t));   // (shift^n w_B^t) R
     return mont_inv(bb_sub(xnR, BB_R1));
 }
+TOYNI_HD uint32_t quotient_zh_inv(const QuotientArgs& a, uint32_t t) { return zh_inv_class(a.shift_nR, a.wBR, t); }
 TOYNI_HD void quotient_one(const QuotientArgs& a, uint64_t i, uint32_t t0, uint32_t t1, uint32_t t2, uint32_t zh_invR, uint32_t& c, uint32_t& q) {
     const uint32_t xR = domain_point_mont(a.dom, i);
     const uint32_t fib = bb_sub(t2, bb_add(t1, t0));                      // fibonacci_constraint, :313-315
@@ -204,6 +205,172 @@ TOYNI_HD void deep_combine_group(const DeepCombineArgs& a, const DeepTerm* terms
     deep_point_inverses<K>(a.dom, a.wNR, a.zR, i0, invR);
 #pragma unroll
     for (int j = 0; j < K; ++j) d[j] = mont_mul(bb_sub(sum[j], a.claim), invR[j]);
+}
+
+// ---- constraint programs of any AIR over up to four column-major matrices (include/toyni_hip.h 3f) ----
+//   c_i = sum_{EMIT k, b = 0} weights[k] value_k(i),   q_i = c_i / (x_i^n - 1) + sum_{EMIT k, b = 1} weights[k] value_k(i)
+// A straight-line program, the same in every lane, is interpreted once per group of K consecutive points.  Its registers hold
+// MONTGOMERY forms (a cell is converted when it is read, constants are converted on the host, x_i and the inverses come out of the
+// domain table in that form), so MUL is one mont_mul; the weights stay plain, so that an EMIT's product is a plain residue.
+// The register file is indexed by program data and therefore lives in memory the caller hands in (LDS on the device): slot r of a
+// thread is the K words at regs[r * stride], stride = K x the workgroup's threads -- every lane of a wave reads its own 4 K
+// consecutive bytes, no bank is asked twice.  The program was validated on the host (toyni_air_program_check): no index is checked here.
+// A word of a table that nothing in the kernel writes, at an address that is the same in every lane: read through the constant
+// address space it is a scalar load whatever else the kernel loads and stores (the compiler proves that by itself only for some shapes)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TOYNI_UNIFORM_LOAD(p) (*reinterpret_cast<const __attribute__((address_space(4))) uint32_t*>((uintptr_t)(p)))
+#else
+#define TOYNI_UNIFORM_LOAD(p) (*(p))
+#endif
+constexpr uint32_t AIR_MAX_REGS = 64, AIR_MAX_MATRICES = 4, AIR_MAX_INSNS = 65536, AIR_INLINE_WEIGHTS = 64;
+constexpr uint32_t AIR_ZH_LDS_CLASSES = 256;   // 1 / Z_H per residue class i mod B sits in LDS up to this B, per thread beyond
+enum : uint32_t { AIR_OP_CELL = 0, AIR_OP_CONST, AIR_OP_X, AIR_OP_XINV, AIR_OP_ADD, AIR_OP_SUB, AIR_OP_MUL, AIR_OP_EMIT, AIR_OP_COUNT };
+struct AirInsn {
+    uint32_t w0;             // op | dst << 8 | a << 16 | b << 24
+    uint32_t imm;            // CONST, XINV: Montgomery form
+};
+struct AirArgs {
+    const AirInsn* insns;
+    const uint32_t* mat[AIR_MAX_MATRICES];      // element (i, c) of matrix m at mat[m][c * col_stride[m] + i]
+    uint64_t col_stride[AIR_MAX_MATRICES];
+    uint32_t* c_out;         // may be null
+    uint32_t* q_out;
+    DomainArgs dom;
+    uint32_t ninsns, nregs;
+    uint32_t log_N, log_blowup;
+    uint32_t wNR;            // Montgomery form of w_N
+    uint32_t shift_nR, wBR;  // as QuotientArgs: x_i^n = shift^n w_B^(i mod B)
+    uint32_t divides;        // some EMIT has b = 0: Z_H is needed (and does not vanish on the coset)
+    uint32_t zh_lds;         // the workgroup keeps 1 / Z_H of all B classes in LDS
+    uint32_t accumulate;
+};
+// The launch shape of a program (host side; tests/emu steps it too).  threads: the largest of 256 / 128 / 64 whose register file,
+// 16 bytes per register and thread, fits AIR_LDS_MAX -- the register file alone decides it.  zh_lds: the B classes of 1 / Z_H go
+// behind the register file when a divided constraint needs them, B <= AIR_ZH_LDS_CLASSES and the bytes that are left hold them;
+// otherwise every thread inverts for its own points.  lds_bytes is what the launch allocates.
+constexpr uint32_t AIR_LDS_MAX = 64u << 10;
+struct AirLaunchShape { uint32_t threads, lds_bytes, zh_lds; };
+inline AirLaunchShape air_launch_shape(uint32_t nregs, uint32_t divides, uint32_t log_blowup) {
+    AirLaunchShape s{256u, 0u, 0u};
+    while (s.threads > 64u && nregs * s.threads * 16u > AIR_LDS_MAX) s.threads >>= 1;
+    s.lds_bytes = nregs * s.threads * 16u;
+    if (divides && log_blowup < 32u && (1ull << log_blowup) <= AIR_ZH_LDS_CLASSES && s.lds_bytes + (4u << log_blowup) <= AIR_LDS_MAX) {
+        s.zh_lds = 1u;
+        s.lds_bytes += 4u << log_blowup;
+    }
+    return s;
+}
+// 1 / Z_H(x_j) R for the K points from i0 on by ONE Fermat inversion (no factor is zero: the host refuses a coset Z_H vanishes on)
+template <int K>
+TOYNI_HD void air_zh_inverses(const AirArgs& a, uint64_t i0, uint32_t (&zhR)[K]) {
+    uint32_t z[K], pre[K];
+    uint32_t xnR = mont_mul(a.shift_nR, mont_pow(a.wBR, i0 & (((uint64_t)1 << a.log_blowup) - 1)));
+    uint32_t acc = BB_R1;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        z[j] = bb_sub(xnR, BB_R1);
+        pre[j] = acc;
+        acc = mont_mul(acc, z[j]);
+        if (j + 1 < K) xnR = mont_mul(xnR, a.wBR);   // w_B^B = 1: running past a class boundary wraps by itself
+    }
+    uint32_t inv = mont_inv(acc);
+#pragma unroll
+    for (int j = K - 1; j >= 0; --j) {
+        zhR[j] = mont_mul(inv, pre[j]);
+        inv = mont_mul(inv, z[j]);
+    }
+}
+// the K words of one cell for the points i0 .. i0 + K - 1 (i0 and N multiples of K): one 16-byte load under deep_term_load's
+// conditions (the column's first word 16-byte aligned, the distance a multiple of 4), word loads otherwise
+template <int K>
+TOYNI_HD void air_cell_load(const AirArgs& a, uint32_t m, uint32_t column, uint32_t rotation, uint64_t i0, uint32_t (&v)[K]) {
+    const uint64_t mask = ((uint64_t)1 << a.log_N) - 1;
+    const uint32_t* col = a.mat[m] + (uint64_t)column * a.col_stride[m];
+    const uint64_t rot = (uint64_t)rotation << a.log_blowup;   // < N
+    if (K == 4 && !(((uintptr_t)col & 15) | (rot & 3u))) {
+        const DeepQuad w = *reinterpret_cast<const DeepQuad*>(col + ((i0 + rot) & mask));
+#pragma unroll
+        for (int j = 0; j < K; ++j) v[j] = w[j & 3];
+    } else {
+#pragma unroll
+        for (int j = 0; j < K; ++j) v[j] = col[(i0 + (uint64_t)j + rot) & mask];
+    }
+}
+template <int K>
+TOYNI_HD void air_reg_load(const uint32_t* regs, uint32_t stride, uint32_t r, uint32_t (&v)[K]) {
+    if (K == 4) {
+        const DeepQuad w = *reinterpret_cast<const DeepQuad*>(regs + r * stride);
+#pragma unroll
+        for (int j = 0; j < K; ++j) v[j] = w[j & 3];
+    } else {
+#pragma unroll
+        for (int j = 0; j < K; ++j) v[j] = regs[r * stride + j];
+    }
+}
+template <int K>
+TOYNI_HD void air_reg_store(uint32_t* regs, uint32_t stride, uint32_t r, const uint32_t (&v)[K]) {
+    if (K == 4) {
+        *reinterpret_cast<DeepQuad*>(regs + r * stride) = DeepQuad{v[0], v[1 % K], v[2 % K], v[3 % K]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < K; ++j) regs[r * stride + j] = v[j];
+    }
+}
+// zhR: 1 / Z_H of the K points (unused without a divided constraint).  c and q come out as plain canonical residues.
+template <int K>
+TOYNI_HD void air_eval_group(const AirArgs& a, const uint32_t* weights, uint32_t* regs, uint32_t stride, uint64_t i0, const uint32_t (&zhR)[K],
+                             uint32_t (&c)[K], uint32_t (&q)[K]) {
+    uint32_t xR[K], undiv[K];
+    xR[0] = domain_point_mont(a.dom, i0);
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        if (j) xR[j] = mont_mul(xR[j - 1], a.wNR);
+        c[j] = 0u;
+        undiv[j] = 0u;
+    }
+    for (uint32_t pc = 0; pc < a.ninsns; ++pc) {
+        const uint32_t w0 = TOYNI_UNIFORM_LOAD(&a.insns[pc].w0), imm = TOYNI_UNIFORM_LOAD(&a.insns[pc].imm);   // the same in every lane
+        const uint32_t op = w0 & 255u, dst = (w0 >> 8) & 255u, ra = (w0 >> 16) & 255u, rb = w0 >> 24;
+        uint32_t v[K];
+        if (op == AIR_OP_EMIT) {
+            const uint32_t wt = TOYNI_UNIFORM(weights[imm]);   // (the inline table is a kernel argument: taking its address as a number would spill it)
+            air_reg_load<K>(regs, stride, ra, v);
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const uint32_t term = mont_mul(wt, v[j]);   // plain weight x Montgomery value = plain product
+                if (rb) undiv[j] = bb_add(undiv[j], term);
+                else c[j] = bb_add(c[j], term);
+            }
+            continue;
+        }
+        if (op >= AIR_OP_ADD) {
+            uint32_t u[K], w[K];
+            air_reg_load<K>(regs, stride, ra, u);
+            air_reg_load<K>(regs, stride, rb, w);
+            if (op == AIR_OP_MUL) {   // op is uniform: three branches, not three results and a select
+#pragma unroll
+                for (int j = 0; j < K; ++j) v[j] = mont_mul(u[j], w[j]);
+            } else if (op == AIR_OP_ADD) {
+#pragma unroll
+                for (int j = 0; j < K; ++j) v[j] = bb_add(u[j], w[j]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < K; ++j) v[j] = bb_sub(u[j], w[j]);
+            }
+        } else if (op == AIR_OP_CELL) {
+            air_cell_load<K>(a, rb, imm, ra, i0, v);
+#pragma unroll
+            for (int j = 0; j < K; ++j) v[j] = to_mont(v[j]);
+        } else if (op == AIR_OP_XINV) {
+            deep_point_inverses<K>(a.dom, a.wNR, imm, i0, v);
+        } else {
+#pragma unroll
+            for (int j = 0; j < K; ++j) v[j] = op == AIR_OP_X ? xR[j] : imm;
+        }
+        air_reg_store<K>(regs, stride, dst, v);
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j) q[j] = a.divides ? bb_add(mont_mul(c[j], zhR[j]), undiv[j]) : undiv[j];
 }
 
 // ---- polynomial evaluation at up to POLY_MAX_POINTS points ----

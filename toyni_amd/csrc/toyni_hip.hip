@@ -765,6 +765,68 @@ constexpr uint32_t DEEP_INLINE_TERMS = 64;
 struct DeepInlineTerms { DeepTerm t[DEEP_INLINE_TERMS]; };
 __global__ void __launch_bounds__(256) deep_combine_inline_kernel(const DeepCombineArgs a, const DeepInlineTerms in) { deep_combine_body(a, in.t); }
 
+// Constraint program of an AIR (prover_kernels.hpp): one group of 4 consecutive points per thread, single points below N = 4.  No
+// grid-stride loop: every read of the program and of the weights precedes the thread's only global stores, so both are fetched
+// by scalar loads.  Dynamic LDS: [nregs][threads] slots of 16 bytes (the register file, sized from the program), then 1 / Z_H of
+// the B residue classes when they fit (a.zh_lds).
+extern __shared__ __align__(16) uint32_t air_lds[];
+__device__ __forceinline__ void air_quotient_body(const AirArgs& a, const uint32_t* weights) {
+    constexpr int K = 4;
+    const uint32_t B = 1u << a.log_blowup;
+    uint32_t* zh_lds = air_lds + a.nregs * blockDim.x * K;
+    if (a.zh_lds) {
+        for (uint32_t t = threadIdx.x; t < B; t += blockDim.x) zh_lds[t] = zh_inv_class(a.shift_nR, a.wBR, t);
+        __syncthreads();
+    }
+    const uint64_t N = (uint64_t)1 << a.log_N;
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a.log_N >= 2) {
+        if (g >= N / K) return;
+        const uint64_t i0 = g * K;
+        uint32_t zhR[K], c[K], q[K];
+        if (a.zh_lds) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) zhR[j] = zh_lds[(i0 + j) & (B - 1)];
+        } else if (a.divides) {
+            air_zh_inverses<K>(a, i0, zhR);
+        } else {
+#pragma unroll
+            for (int j = 0; j < K; ++j) zhR[j] = 0u;
+        }
+        air_eval_group<K>(a, weights, air_lds + threadIdx.x * K, blockDim.x * K, i0, zhR, c, q);
+        uint32_t* outs[2] = {a.c_out, a.q_out};
+#pragma unroll
+        for (int o = 0; o < 2; ++o) {
+            uint32_t* dst = outs[o];
+            if (!dst) continue;
+            uint32_t (&v)[K] = o ? q : c;
+            if (!((uintptr_t)dst & 15)) {
+                uint4* d4 = reinterpret_cast<uint4*>(dst + i0);
+                if (a.accumulate) {
+                    const uint4 p = *d4;
+                    v[0] = bb_add(p.x, v[0]); v[1] = bb_add(p.y, v[1]); v[2] = bb_add(p.z, v[2]); v[3] = bb_add(p.w, v[3]);
+                }
+                *d4 = make_uint4(v[0], v[1], v[2], v[3]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < K; ++j) dst[i0 + j] = a.accumulate ? bb_add(dst[i0 + j], v[j]) : v[j];
+            }
+        }
+    } else if (g < N) {
+        uint32_t zhR[1] = {0u}, c[1], q[1];
+        if (a.zh_lds) zhR[0] = zh_lds[g & (B - 1)];
+        else if (a.divides) air_zh_inverses<1>(a, g, zhR);
+        air_eval_group<1>(a, weights, air_lds + threadIdx.x, blockDim.x, g, zhR, c, q);
+        if (a.c_out) a.c_out[g] = a.accumulate ? bb_add(a.c_out[g], c[0]) : c[0];
+        a.q_out[g] = a.accumulate ? bb_add(a.q_out[g], q[0]) : q[0];
+    }
+}
+// the weights in device memory (any number) ...
+__global__ void __launch_bounds__(256) air_quotient_kernel(const AirArgs a, const uint32_t* __restrict__ weights) { air_quotient_body(a, weights); }
+// ... or, up to AIR_INLINE_WEIGHTS of them, inside the kernel arguments (as deep_combine_inline_kernel)
+struct AirInlineWeights { uint32_t w[AIR_INLINE_WEIGHTS]; };
+__global__ void __launch_bounds__(256) air_quotient_inline_kernel(const AirArgs a, const AirInlineWeights in) { air_quotient_body(a, in.w); }
+
 // Merkle openings: one thread per (opening, level) copies the sibling digest; one thread per opening adds salt, value, flags
 struct OpenGroup {
     const Digest* levels;
@@ -3107,6 +3169,158 @@ int toyni_deep_combine_device(toyni_ntt_ctx* c, const uint32_t* d_values, size_t
     std::memcpy(h, table.data(), nterms * sizeof(DeepTerm));
     HIPCHK(hipMemcpyAsync(sc.d_lde32, h, nterms * sizeof(DeepTerm), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(deep_combine_kernel, grid, dim3(256), 0, s, a, reinterpret_cast<const DeepTerm*>(sc.d_lde32));
+    return (int)hipGetLastError();
+}
+
+// ---- section 3f: constraint programs ----
+struct toyni_air_program {
+    int device = 0;
+    toyni_air_info info{};
+    AirInsn* d_insns = nullptr;
+};
+
+int toyni_air_program_check(const toyni_air_insn* insns, size_t ninsns, toyni_air_info* info) {
+    if (!insns || !info) return TOYNI_E_NULL;
+    if (ninsns == 0 || ninsns > AIR_MAX_INSNS) return TOYNI_E_RANGE;
+    toyni_air_info r{};
+    r.ninsns = (uint32_t)ninsns;
+    bool written[AIR_MAX_REGS] = {};
+    bool emitted = false;
+    const auto readable = [&](uint8_t reg) { return reg < AIR_MAX_REGS && written[reg]; };
+    for (size_t k = 0; k < ninsns; ++k) {
+        const toyni_air_insn& in = insns[k];
+        if (in.op >= AIR_OP_COUNT) return TOYNI_E_RANGE;
+        if (in.op == TOYNI_AIR_EMIT) {
+            if (!readable(in.a) || in.b > 1 || in.imm >= 65536) return TOYNI_E_RANGE;
+            r.nconstraints = std::max(r.nconstraints, in.imm + 1);
+            if (in.b == 0) r.divides_by_zh = 1;
+            emitted = true;
+            continue;
+        }
+        if (in.dst >= AIR_MAX_REGS) return TOYNI_E_RANGE;
+        if (in.op >= TOYNI_AIR_ADD) {
+            if (!readable(in.a) || !readable(in.b)) return TOYNI_E_RANGE;
+        } else if (in.op == TOYNI_AIR_CELL) {
+            if (in.b >= AIR_MAX_MATRICES || in.imm >= 65536) return TOYNI_E_RANGE;
+            r.nmatrices = std::max<uint32_t>(r.nmatrices, in.b + 1u);
+            r.min_width[in.b] = std::max(r.min_width[in.b], in.imm + 1);
+            r.max_rotation = std::max<uint32_t>(r.max_rotation, in.a);
+        } else if (in.op != TOYNI_AIR_X && in.imm >= BB_P) {   // CONST, XINV
+            return TOYNI_E_RANGE;
+        }
+        written[in.dst] = true;
+    }
+    if (!emitted) return TOYNI_E_RANGE;
+    for (uint32_t k = 0; k < AIR_MAX_REGS; ++k)
+        if (written[k]) r.nregs = k + 1;   // a register that is read has been written
+    *info = r;
+    return TOYNI_OK;
+}
+
+int toyni_air_program_create(toyni_ntt_ctx* c, const toyni_air_insn* insns, size_t ninsns, toyni_air_program** out) {
+    if (!c || !insns || !out) return TOYNI_E_NULL;
+    toyni_air_info info{};
+    if (int rc = toyni_air_program_check(insns, ninsns, &info)) return rc;
+    std::vector<AirInsn> dev(ninsns);
+    for (size_t k = 0; k < ninsns; ++k) {
+        const toyni_air_insn& in = insns[k];
+        dev[k].w0 = (uint32_t)in.op | (uint32_t)in.dst << 8 | (uint32_t)in.a << 16 | (uint32_t)in.b << 24;
+        dev[k].imm = (in.op == TOYNI_AIR_CONST || in.op == TOYNI_AIR_XINV) ? to_mont_host(in.imm) : in.imm;
+    }
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    toyni_air_program* p = new toyni_air_program();
+    p->device = c->device;
+    p->info = info;
+    hipError_t e = hipMalloc((void**)&p->d_insns, ninsns * sizeof(AirInsn));
+    if (e == hipSuccess) e = hipMemcpy(p->d_insns, dev.data(), ninsns * sizeof(AirInsn), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (p->d_insns) (void)hipFree(p->d_insns);
+        delete p;
+        return (int)e;
+    }
+    *out = p;
+    return TOYNI_OK;
+}
+
+int toyni_air_program_destroy(toyni_air_program* p) {
+    if (!p) return TOYNI_OK;
+    DeviceGuard guard(p->device);
+    (void)hipDeviceSynchronize();   // a call in flight may still read the program
+    const hipError_t e = hipFree(p->d_insns);
+    delete p;
+    return (int)e;
+}
+
+int toyni_air_program_info(const toyni_air_program* p, toyni_air_info* info) {
+    if (!p || !info) return TOYNI_E_NULL;
+    *info = p->info;
+    return TOYNI_OK;
+}
+
+int toyni_air_quotient_device(toyni_ntt_ctx* c, const toyni_air_program* prog, const toyni_air_matrix* mats, size_t nmats, unsigned log_blowup,
+                              uint32_t shift, const uint32_t* weights, size_t nweights, uint32_t* d_c_out, uint32_t* d_q_out, int accumulate,
+                              void* stream) {
+    if (!c || !prog || !weights || !d_q_out || (!mats && nmats)) return TOYNI_E_NULL;
+    const toyni_air_info& info = prog->info;
+    const int log_N = c->plan.log_n;
+    const uint64_t N = 1ull << log_N;
+    if (prog->device != c->device || nmats < info.nmatrices || nmats > AIR_MAX_MATRICES || (int)log_blowup > log_N || shift == 0 || shift >= BB_P ||
+        nweights < info.nconstraints || nweights > 65536 || (((uintptr_t)d_c_out | (uintptr_t)d_q_out) & 3))
+        return TOYNI_E_RANGE;
+    if (info.max_rotation >= (N >> log_blowup)) return TOYNI_E_RANGE;
+    for (uint32_t m = 0; m < info.nmatrices; ++m)
+        if (info.min_width[m] && (!mats[m].d_values || ((uintptr_t)mats[m].d_values & 3) || mats[m].width < info.min_width[m] || mats[m].width > 65536 ||
+                                  mats[m].col_stride < N))
+            return TOYNI_E_RANGE;
+    for (size_t k = 0; k < nweights; ++k)
+        if (weights[k] >= BB_P) return TOYNI_E_RANGE;
+    const uint64_t n = N >> log_blowup;
+    const uint32_t shift_n = bb_pow_host(shift, n);
+    // Z_H(x) = 0 on the coset only if shift^n is a B-th root of unity (toyni_fib_quotient_device)
+    if (info.divides_by_zh && bb_pow_host(shift_n, 1ull << log_blowup) == 1u) return TOYNI_E_ZERO_INVERSE;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    AirArgs a{};
+    a.insns = prog->d_insns;
+    for (uint32_t m = 0; m < info.nmatrices; ++m) {
+        a.mat[m] = info.min_width[m] ? mats[m].d_values : nullptr;
+        a.col_stride[m] = mats[m].col_stride;
+    }
+    a.c_out = d_c_out;
+    a.q_out = d_q_out;
+    a.dom = domain_args(c, (unsigned)log_N, shift);
+    a.ninsns = info.ninsns;
+    a.nregs = info.nregs;
+    a.log_N = (uint32_t)log_N;
+    a.log_blowup = log_blowup;
+    a.wNR = to_mont_host(bb_root_of_unity_host((uint32_t)log_N));
+    a.shift_nR = to_mont_host(shift_n);
+    a.wBR = to_mont_host(bb_pow_host(bb_root_of_unity_host((uint32_t)log_N), n));
+    a.divides = info.divides_by_zh;
+    a.accumulate = accumulate ? 1u : 0u;
+    const AirLaunchShape shape = air_launch_shape(info.nregs, info.divides_by_zh, log_blowup);   // prover_kernels.hpp
+    const unsigned threads = shape.threads;
+    const size_t lds = shape.lds_bytes;
+    a.zh_lds = shape.zh_lds;
+    const uint64_t items = log_N >= 2 ? N / 4 : N;
+    const dim3 grid((unsigned)((items + threads - 1) / threads));
+    if (nweights <= AIR_INLINE_WEIGHTS) {   // the weights ride in the kernel arguments
+        AirInlineWeights in{};
+        std::copy(weights, weights + nweights, in.w);
+        hipLaunchKernelGGL(air_quotient_inline_kernel, grid, dim3(threads), lds, s, a, in);
+        return (int)hipGetLastError();
+    }
+    // more weights: pinned staging ring -> the stream's intermediate buffer by a stream-ordered copy (toyni_deep_combine_device)
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words, nweights, sizeof(uint32_t));
+    if (rc) return rc;
+    void* h = nullptr;
+    if ((rc = ring_slice(sc, s, nweights * sizeof(uint32_t), &h))) return rc;
+    std::memcpy(h, weights, nweights * sizeof(uint32_t));
+    HIPCHK(hipMemcpyAsync(sc.d_lde32, h, nweights * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(air_quotient_kernel, grid, dim3(threads), lds, s, a, sc.d_lde32);
     return (int)hipGetLastError();
 }
 

@@ -91,6 +91,165 @@ def deep_combine_device(ctx, d_values: int, width: int, col_stride: int, log_blo
                                         1 if accumulate else 0, d_out, stream or None), "GPU DEEP combination failed")
 
 
+# ---- constraint programs (include/toyni_hip.h 3f) ----
+AIR_CELL, AIR_CONST, AIR_X, AIR_XINV, AIR_ADD, AIR_SUB, AIR_MUL, AIR_EMIT = range(8)
+AIR_MAX_REGS, AIR_MAX_MATRICES = 64, 4
+_P = 2013265921
+
+
+class AirInsn(ctypes.Structure):   # toyni_air_insn
+    _fields_ = [("op", ctypes.c_uint8), ("dst", ctypes.c_uint8), ("a", ctypes.c_uint8), ("b", ctypes.c_uint8), ("imm", ctypes.c_uint32)]
+
+
+class AirMatrix(ctypes.Structure):   # toyni_air_matrix
+    _fields_ = [("d_values", ctypes.c_void_p), ("width", ctypes.c_size_t), ("col_stride", ctypes.c_size_t)]
+
+
+class AirInfo(ctypes.Structure):   # toyni_air_info
+    _fields_ = [("ninsns", ctypes.c_uint32), ("nregs", ctypes.c_uint32), ("nconstraints", ctypes.c_uint32), ("nmatrices", ctypes.c_uint32),
+                ("max_rotation", ctypes.c_uint32), ("divides_by_zh", ctypes.c_uint32), ("min_width", ctypes.c_uint32 * AIR_MAX_MATRICES)]
+
+
+def air_insns(insns):
+    """The instruction array of a constraint program from (op, dst, a, b, imm) tuples."""
+    return (AirInsn * len(insns))(*[AirInsn(int(op), int(dst), int(a), int(b), int(imm)) for op, dst, a, b, imm in insns])
+
+
+def air_program_check(insns) -> AirInfo:
+    """toyni_air_program_check: host only.  insns: what air_insns returns, or the tuples it takes."""
+    arr = insns if isinstance(insns, ctypes.Array) else air_insns(insns)
+    info = AirInfo()
+    check(lib.toyni_air_program_check(arr if len(arr) else None, len(arr), ctypes.byref(info)), "constraint program refused")
+    return info
+
+
+class AirProgram:
+    """A validated constraint program on ctx's device (toyni_air_program_create); a context manager."""
+
+    def __init__(self, ctx, insns):
+        arr = insns if isinstance(insns, ctypes.Array) else air_insns(insns)
+        h = ctypes.c_void_p()
+        check(lib.toyni_air_program_create(ctx.handle, arr if len(arr) else None, len(arr), ctypes.byref(h)), "constraint program refused")
+        self.handle = h
+        self.info = AirInfo()
+        check(lib.toyni_air_program_info(h, ctypes.byref(self.info)), "constraint program info failed")
+
+    def destroy(self) -> None:
+        if self.handle:
+            lib.toyni_air_program_destroy(self.handle)
+            self.handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.destroy()
+
+
+def air_quotient_device(ctx, prog, mats, log_blowup: int, shift: int, weights, d_q_out: int, d_c_out: int = 0, accumulate: bool = False,
+                        stream=None) -> None:
+    """Runs the program at every point of the LDE coset (include/toyni_hip.h 3f): d_q_out (+)= c / Z_H + the undivided constraints,
+    d_c_out (+)= c.  mats: up to four (d_values, width, col_stride) column-major matrices; weights: one per constraint number."""
+    m = (AirMatrix * len(mats))(*[AirMatrix(d or None, w, cs) for d, w, cs in mats])
+    w = np.ascontiguousarray(weights, dtype=np.uint32)
+    check(lib.toyni_air_quotient_device(ctx.handle, prog.handle, m if len(mats) else None, len(mats), log_blowup, shift, w.ctypes.data, w.size,
+                                        d_c_out or None, d_q_out, 1 if accumulate else 0, stream or None), "GPU constraint program failed")
+
+
+class AirExpr:
+    """A node of AirBuilder's expression graph: key = (op, operand nodes or fields...)."""
+
+    def __init__(self, builder, key):
+        self.builder, self.key = builder, key
+
+    def _bin(self, op, other, swap=False):
+        o = other if isinstance(other, AirExpr) else self.builder.const(other)
+        return self.builder._node((op, o, self) if swap else (op, self, o))
+
+    def __add__(self, o): return self._bin(AIR_ADD, o)
+    def __radd__(self, o): return self._bin(AIR_ADD, o, True)
+    def __sub__(self, o): return self._bin(AIR_SUB, o)
+    def __rsub__(self, o): return self._bin(AIR_SUB, o, True)
+    def __mul__(self, o): return self._bin(AIR_MUL, o)
+    def __rmul__(self, o): return self._bin(AIR_MUL, o, True)
+
+
+class AirBuilder:
+    """Expressions -> a constraint program.  cell / const / x / xinv return expressions that support + - * (ints become constants);
+    emit records a constraint; compile shares common subexpressions (equal nodes are one object), orders the nodes so that operands
+    come first, and gives every node a register that is free again after the node's last use."""
+
+    def __init__(self):
+        self.nodes, self.emits = {}, []
+
+    def _node(self, key):
+        ident = tuple(id(k) if isinstance(k, AirExpr) else k for k in key)   # operands are already unique objects
+        if ident not in self.nodes:
+            self.nodes[ident] = AirExpr(self, key)
+        return self.nodes[ident]
+
+    def cell(self, matrix, column, rotation=0): return self._node((AIR_CELL, int(matrix), int(column), int(rotation)))
+    def const(self, v): return self._node((AIR_CONST, int(v) % _P))
+    def x(self): return self._node((AIR_X,))
+    def xinv(self, v): return self._node((AIR_XINV, int(v) % _P))
+
+    def emit(self, k, expr, divide=True):
+        self.emits.append((int(k), expr if isinstance(expr, AirExpr) else self.const(expr), bool(divide)))
+
+    def compile(self):
+        """-> list of (op, dst, a, b, imm) tuples (air_insns takes them).  ValueError beyond 64 live registers."""
+        order, seen = [], set()
+        for _, root, _ in self.emits:             # operands first, depth first, without recursion (a long sum is a deep chain)
+            stack = [(root, False)]
+            while stack:
+                node, done = stack.pop()
+                if done:
+                    order.append(node)
+                elif id(node) not in seen:
+                    seen.add(id(node))
+                    stack.append((node, True))
+                    stack.extend((k, False) for k in reversed(node.key[1:]) if isinstance(k, AirExpr))
+        steps = [("node", nd) for nd in order]
+        pos = {id(nd): i for i, nd in enumerate(order)}
+        for k, root, divide in self.emits:        # an EMIT goes right after its value, so the value's register is free early
+            steps.append(("emit", (k, root, divide, pos[id(root)])))
+        steps.sort(key=lambda s: (pos[id(s[1])], 0) if s[0] == "node" else (s[1][3], 1))
+        last = {}
+        for i, (kind, what) in enumerate(steps):
+            for k in (what.key[1:] if kind == "node" else (what[1],)):
+                if isinstance(k, AirExpr):
+                    last[id(k)] = i
+        free, reg, insns = list(range(AIR_MAX_REGS - 1, -1, -1)), {}, []
+        for i, (kind, what) in enumerate(steps):
+            if kind == "emit":
+                k, root, divide, _ = what
+                insns.append((AIR_EMIT, 0, reg[id(root)], 0 if divide else 1, k))
+                ops = [root]
+            else:
+                ops = [k for k in what.key[1:] if isinstance(k, AirExpr)]
+            srcs = [reg[id(k)] for k in ops]
+            for k in {id(k): k for k in ops}.values():           # operands whose last use this is give their register to the result
+                if last[id(k)] == i:
+                    free.append(reg[id(k)])
+            if kind == "emit":
+                continue
+            if not free:
+                raise ValueError("the program needs more than 64 live registers")
+            dst = reg[id(what)] = free.pop()
+            op = what.key[0]
+            if op == AIR_CELL:
+                insns.append((op, dst, what.key[3], what.key[1], what.key[2]))
+            elif op in (AIR_CONST, AIR_XINV):
+                insns.append((op, dst, 0, 0, what.key[1]))
+            elif op == AIR_X:
+                insns.append((op, dst, 0, 0, 0))
+            else:
+                insns.append((op, dst, srcs[0], srcs[1], 0))
+            if id(what) not in last:                             # unreachable for emitted roots; kept for safety of the free list
+                free.append(dst)
+        return insns
+
+
 def merkle_open_record_bytes(n: int) -> int:
     return lib.toyni_merkle_open_record_bytes(n)
 
