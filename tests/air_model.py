@@ -1,5 +1,6 @@
-"""The instruction set of constraint programs (include/toyni_hip.h 3f) as a vectorised numpy model, plus generators of programs.
-Shared by the tests of the AIR quotient; imports nothing from the library."""
+"""The instruction set of constraint programs (include/toyni_hip.h 3f) as a vectorised numpy model, plus generators of programs, the
+model of the multi-column DEEP combination (3e) and the launcher's sizing rule restated.  Shared by the tests of the AIR quotient, the
+DEEP combination and the two-column proof; imports nothing from the library."""
 import numpy as np
 
 P = 2013265921
@@ -24,6 +25,24 @@ def coset_points(n, shift):
     while xs.size < n:
         xs = np.concatenate([xs, xs * np.uint64(pow(w, xs.size, P)) % np.uint64(P)])
     return xs
+
+
+def deep_model(m, terms, blowup, shift, z):
+    """m: (width, N) uint64 canonical; terms: (column, rotation, alpha, value).  x_i = z gives 0 (Fermat: 0^(p-2) = 0)."""
+    n = m.shape[1]
+    num = np.zeros(n, dtype=np.uint64)
+    for c, rot, a, v in terms:
+        col = np.roll(m[c], -(rot * blowup) % n)
+        num = (num + (col + np.uint64(P - v)) % np.uint64(P) * np.uint64(a)) % np.uint64(P)
+    den = (coset_points(n, shift) + np.uint64(P - z)) % np.uint64(P)
+    return (num * powmod_vec(den, P - 2) % np.uint64(P)).astype(np.uint32)
+
+
+def air_launch_shape(nregs, divides, log_b):
+    """air_launch_shape (toyni_amd/csrc/prover_kernels.hpp) restated: (threads, dynamic LDS bytes, the 1 / Z_H class table is in LDS)."""
+    threads = next(t for t in (256, 128, 64) if nregs * t * 16 <= 65536 or t == 64)
+    zh = int(bool(divides) and log_b <= 8 and nregs * threads * 16 + (4 << log_b) <= 65536)
+    return threads, nregs * threads * 16 + zh * (4 << log_b), zh
 
 
 def air_model(insns, mats, n_points, log_blowup, shift, weights):

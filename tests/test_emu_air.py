@@ -10,7 +10,7 @@ import subprocess
 
 import numpy as np
 
-from air_model import EMIT, XINV, P, air_model, coset_points, fib_program
+from air_model import EMIT, XINV, P, air_launch_shape, air_model, coset_points, fib_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "toyni_amd", "csrc")
@@ -43,9 +43,8 @@ def test_interpreter_body_matches_the_model_on_cpu():
     recs = [r for r in recs if r[0] != "SHAPE"]
     assert len(shapes_seen) == 64 * 2 * 5
     for nregs, divides, log_b, threads, lds, zh in shapes_seen:       # the launcher's sizing rule, restated
-        want_threads = next(t for t in (256, 128, 64) if nregs * t * 16 <= 65536 or t == 64)
-        want_zh = int(bool(divides) and log_b <= 8 and nregs * want_threads * 16 + (4 << log_b) <= 65536)
-        assert (threads, zh, lds) == (want_threads, want_zh, nregs * want_threads * 16 + want_zh * (4 << log_b)), (nregs, divides, log_b)
+        want_threads, want_lds, want_zh = air_launch_shape(nregs, divides, log_b)            # tests/air_model.py
+        assert (threads, zh, lds) == (want_threads, want_zh, want_lds), (nregs, divides, log_b)
         assert 0 < lds <= 65536 and threads % 64 == 0
     assert (16, 1, 5, 256, 65536, 0) in shapes_seen and (15, 1, 5, 256, 61568, 1) in shapes_seen and (64, 1, 0, 64, 65536, 0) in shapes_seen
     while k < len(recs):

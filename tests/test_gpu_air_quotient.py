@@ -1,6 +1,7 @@
 """Constraint programs evaluated into the quotient codeword on the device (include/toyni_hip.h 3f):
   1. the 13-instruction Fibonacci program equals toyni_fib_quotient_device and oracle.fib_quotient word for word (c and q)
-  2. random programs against the numpy model of the instruction set (tests/air_model.py, nothing from the library)
+  2. random programs against the numpy model of the instruction set (tests/air_model.py, nothing from the library), and once more
+     at every launch shape the sizing rule can pick: 256 / 128 / 64 threads x where 1 / Z_H comes from
   3. the pipeline property: the quotient of a true two-column trace is a polynomial of degree < n
   4. guard bands around every matrix and both outputs, two fillings, same outputs
   5. every refusal of the header, the outputs untouched
@@ -11,7 +12,7 @@ import numpy as np
 import pytest
 
 import oracle
-from air_model import CELL, CONST, EMIT, GEN_2_27, P, X, XINV, air_model, coset_points, fib_program, random_program
+from air_model import CELL, CONST, EMIT, GEN_2_27, P, X, XINV, air_launch_shape, air_model, coset_points, fib_program, random_program
 from guarded import DevMem, Guarded
 
 pytestmark = pytest.mark.gpu
@@ -121,11 +122,12 @@ GENERAL = [
 ]
 
 
-@pytest.mark.parametrize("log_N,log_b,nmats,nregs,length,nweights,off,on_coset", GENERAL)
-def test_random_programs_match_the_numpy_model(ta, dev, log_N, log_b, nmats, nregs, length, nweights, off, on_coset):
+def check_random_program(ta, dev, log_N, log_b, nmats, nregs, length, nweights, off, on_coset, seed, divides=True):
+    """One random program: the first call, an accumulating second with other weights, a third that leaves c alone -- c and q word for
+    word against the numpy model.  divides = False: every constraint is emitted undivided."""
     N = 1 << log_N
     rows = N >> log_b
-    rng = np.random.default_rng(9000 + 100 * log_N + 10 * nmats + nregs)
+    rng = np.random.default_rng(seed)
     widths = [[1, 3, 64][(m + log_N) % 3] for m in range(nmats)]
     strides = [N + 20 if m == nmats - 1 and (nmats > 1 or log_N % 2) else N for m in range(nmats)]
     mats = [rand_field(rng, w, N) for w in widths]
@@ -136,7 +138,7 @@ def test_random_programs_match_the_numpy_model(ta, dev, log_N, log_b, nmats, nre
         insns = [(CELL, 0, 0, 0, 0), (EMIT, 0, 0, 0, 0)]
     else:
         ncons = 100 if (nweights, length) == (100, 3000) else 3    # 101 EMITs would leave a 40-instruction program no room for anything else
-        insns = random_program(rng, nregs, length, widths, rows, ncons, point, may_divide=not on_coset)
+        insns = random_program(rng, nregs, length, widths, rows, ncons, point, may_divide=divides and not on_coset)
         assert len(insns) == max(length, nregs + ncons + 1)
     ops = {i[0] for i in insns}
     assert length == 2 or (ops == set(range(8)) if nregs > 1 else EMIT in ops)
@@ -148,6 +150,7 @@ def test_random_programs_match_the_numpy_model(ta, dev, log_N, log_b, nmats, nre
         d_q, d_c = dev.alloc(N, (off + 4) % 16), dev.alloc(N, (off + 8) % 16)
         with ta.prover.AirProgram(ctx, insns) as prog:
             assert prog.info.nregs == (1 if length == 2 else nregs) and prog.info.ninsns == len(insns)
+            assert length == 2 or prog.info.divides_by_zh == int(divides and not on_coset)
             ta.prover.air_quotient_device(ctx, prog, d_mats, log_b, shift, w1, d_q, d_c_out=d_c)
             c1, q1 = dev.down(d_c, N), dev.down(d_q, N)
             want_c1, want_q1 = air_model(insns, mats, N, log_b, shift, w1)
@@ -164,6 +167,58 @@ def test_random_programs_match_the_numpy_model(ta, dev, log_N, log_b, nmats, nre
             assert (q2 == ((2 * want_q1.astype(np.uint64) + want_q2) % P).astype(np.uint32)).all()
     finally:
         ctx.destroy()
+
+
+@pytest.mark.parametrize("log_N,log_b,nmats,nregs,length,nweights,off,on_coset", GENERAL)
+def test_random_programs_match_the_numpy_model(ta, dev, log_N, log_b, nmats, nregs, length, nweights, off, on_coset):
+    check_random_program(ta, dev, log_N, log_b, nmats, nregs, length, nweights, off, on_coset, seed=9000 + 100 * log_N + 10 * nmats + nregs)
+
+
+# ---- 2b. every launch shape ----
+# air_launch_shape (toyni_amd/csrc/prover_kernels.hpp; restated in tests/air_model.py, held to the emulator's SHAPE lines by
+# tests/test_emu_air.py) picks the workgroup from nregs and decides whether 1 / Z_H of the B residue classes sits in LDS behind the
+# register file, where `for (t = threadIdx.x; t < B; t += blockDim.x)` fills it.  (nregs, log2 B, some constraint is divided), N = 2^12:
+SHAPES = [
+    (16, 3, 1),   # last size on 256 threads: 64 KiB of registers, no room for the table
+    (17, 3, 1),   # first size on 128 threads
+    (31, 8, 1),   # 128 threads, B = 256 > threads: the strided fill
+    (32, 8, 1),   # 128 threads, 64 KiB full: per-group inversion
+    (32, 3, 0),   # 128 threads, nothing divided
+    (33, 7, 1),   # 64 threads, B = 128: the strided fill
+    (63, 8, 1),   # 64 threads, 63 KiB + 1 KiB: exactly 64 KiB of dynamic LDS
+    (63, 9, 1),   # B > 256: no table
+    (64, 2, 1),   # the anchor GENERAL already has: 64 threads, no room
+    # the combinations the nine above leave out
+    (7, 3, 1), (7, 9, 1), (7, 3, 0),      # 256 threads: table in LDS, B > 256, nothing divided
+    (17, 9, 1),                           # 128 threads, B > 256
+    (33, 3, 1), (64, 3, 0),               # 64 threads: table in LDS with B <= threads, nothing divided
+]
+SHAPES_LOG_N = 12
+
+
+def shape_class(nregs, log_b, divides):
+    """(threads, where 1 / Z_H comes from) of a launch."""
+    threads, _lds, zh = air_launch_shape(nregs, divides, log_b)
+    if zh:
+        return threads, "table in LDS, B <= threads" if (1 << log_b) <= threads else "table in LDS, B > threads: strided fill"
+    return threads, "no table: nothing divides" if not divides else "no table: B > 256" if log_b > 8 else "no table: no room"
+
+
+# 3 weights ride in the kernel arguments, 100 come from device memory: two kernels, each compiled with the fill loop of its own
+@pytest.mark.parametrize("nweights", [3, 100])
+@pytest.mark.parametrize("k", range(len(SHAPES)), ids=[f"nregs{r}-logb{b}-div{d}" for r, b, d in SHAPES])
+def test_random_programs_match_the_numpy_model_at_every_launch_shape(ta, dev, k, nweights):
+    nregs, log_b, divides = SHAPES[k]
+    check_random_program(ta, dev, SHAPES_LOG_N, log_b, 2, nregs, 40, nweights, 4 * (k % 4), False, seed=12000 + k, divides=bool(divides))
+
+
+# SHAPES hits every combination the rule can produce at this N -- 3 workgroup sizes x 5 sources of 1 / Z_H, less the one that cannot
+# occur: a 256-thread workgroup never meets B > threads with the table in LDS, because the table is only kept for B <= 256
+REACHABLE = {shape_class(r, b, d) for r in range(1, 65) for b in range(SHAPES_LOG_N + 1) for d in (0, 1)}
+assert (256, "table in LDS, B > threads: strided fill") not in REACHABLE and len(REACHABLE) == 14
+assert {t for t, _ in REACHABLE} == {256, 128, 64}
+assert {shape_class(*s) for s in SHAPES} == REACHABLE
+assert air_launch_shape(63, 1, 8) == (64, 65536, 1) and air_launch_shape(31, 1, 8) == (128, 64512, 1)     # the exact fit; B = 2 x threads
 
 
 # the cases above cover what the module's docstring claims

@@ -11,12 +11,11 @@ import numpy as np
 import pytest
 
 import oracle
+from air_model import GEN_2_27, P, coset_points, deep_model
 from guarded import DevMem, Guarded
 
 pytestmark = pytest.mark.gpu
 
-P = 2013265921
-GEN_2_27 = 440564289
 E_NULL, E_RANGE = 10002, 10006
 SENTINEL_WORD = 0xA5A5A5A5
 
@@ -73,37 +72,7 @@ def dev(ta):
     d.free()
 
 
-# ---- the independent model: numpy only ----
-def powmod_vec(a, e):
-    r = np.ones_like(a, dtype=np.uint64)
-    a = a.astype(np.uint64)
-    while e:
-        if e & 1:
-            r = r * a % np.uint64(P)
-        a = a * a % np.uint64(P)
-        e >>= 1
-    return r
-
-
-def coset_points(n, shift):
-    w = pow(GEN_2_27, (1 << 27) // n, P)
-    xs = np.array([shift], dtype=np.uint64)
-    while xs.size < n:
-        xs = np.concatenate([xs, xs * np.uint64(pow(w, xs.size, P)) % np.uint64(P)])
-    return xs
-
-
-def deep_model(m, terms, blowup, shift, z):
-    """m: (width, N) uint64 canonical; terms: (column, rotation, alpha, value).  x_i = z gives 0 (Fermat: 0^(p-2) = 0)."""
-    n = m.shape[1]
-    num = np.zeros(n, dtype=np.uint64)
-    for c, rot, a, v in terms:
-        col = np.roll(m[c], -(rot * blowup) % n)
-        num = (num + (col + np.uint64(P - v)) % np.uint64(P) * np.uint64(a)) % np.uint64(P)
-    den = (coset_points(n, shift) + np.uint64(P - z)) % np.uint64(P)
-    return (num * powmod_vec(den, P - 2) % np.uint64(P)).astype(np.uint32)
-
-
+# the independent model (numpy only) is deep_model of tests/air_model.py, shared with the oracle-only prover of the two-column proof
 def rand_field(rng, *shape):
     return rng.integers(0, P, shape, dtype=np.uint64)
 
