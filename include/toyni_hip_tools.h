@@ -16,7 +16,10 @@ extern "C" {
 /* Per-pass kernel timing for bench.py's roofline object: launches pass p of `batch` transforms `reps` times
  * between HIP events on `stream` (pass 0 reads d_data, later passes the context's work buffer; values stay
  * canonical but d_data's contents are overwritten).  ms_per_pass[p] = average launch duration in ms for
- * p < toyni_ntt_ctx_passes(ctx).  Blocking. */
+ * p < toyni_ntt_ctx_passes(ctx).  Blocking.
+ * What is timed is the pass plan of the batch's route: the two-pass plan where toyni_ntt_device takes it (n = 2^21 / 2^22), the
+ * main plan otherwise -- ALSO where toyni_ntt_device runs a single sweep instead (n = 2^11 .. 2^15 in large launches, where
+ * toyni_ntt_ctx_passes_for reports 1): the sweep itself is not timed here. */
 int toyni_ntt_profile_passes(toyni_ntt_ctx* ctx, uint32_t* d_data, size_t batch, int inverse, int reps, float* ms_per_pass, void* stream);
 
 /* Launch durations of the pass kernels INSIDE a workload: while enabled, every pass launch this context enqueues

@@ -22,6 +22,7 @@ fn main() {
     println!("cargo:rerun-if-changed=hip/toyni_hip.hip");
     println!("cargo:rerun-if-changed=hip/ntt_kernels.hpp");
     println!("cargo:rerun-if-changed=hip/ntt_plan.hpp");
+    println!("cargo:rerun-if-changed=hip/ntt_route.hpp");
     println!("cargo:rerun-if-changed=hip/bb_field.hpp");
     println!("cargo:rerun-if-changed=hip/merkle_kernels.hpp");
     println!("cargo:rerun-if-changed=hip/multi_gpu.hpp");

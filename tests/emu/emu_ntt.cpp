@@ -46,6 +46,7 @@ static int failures = 0;
 
 // one tile of a pass, phase by phase: every thread runs phase k before any thread runs phase k + 1 (the pass' barriers)
 static unsigned long long tiles_by_steps[4] = {0, 0, 0, 0};
+static LaunchKnobs knobs = launch_knobs();   // the process's dispatch knobs; "pN" / "wN" move two of them
 static bool latency_plan = false;   // "Q1": n = 2^21 / 2^22 through their two-pass plans (2048-point three-step shapes)
 template <class P, int LZ = 0>
 static void emu_tile(const PassArgs& a, uint32_t b, uint32_t* lds) {
@@ -147,7 +148,7 @@ static void emu_transform(const NttPlan& plan, bool inverse, const uint32_t* src
         CHECK(okl, "lds transform rejected log_n=%d", plan.log_n);
         return;
     }
-    bool ok = for_each_pass<LQ>(plan, blob.data(), inverse, src, work, dst, batch, [&](auto pass, auto lzc, const PassArgs& a, uint64_t nblocks) {
+    bool ok = for_each_pass<LQ>(knobs, plan, blob.data(), inverse, src, work, dst, batch, [&](auto pass, auto lzc, const PassArgs& a, uint64_t nblocks) {
         using P = decltype(pass);
         constexpr int LZ = decltype(lzc)::value;
         std::vector<uint32_t> lds(P::LDS_WORDS, 0xDEADBEEFu);  // exact size: an out-of-range LDS word is an ASan error
@@ -165,7 +166,7 @@ static void emu_transform(const NttPlan& plan, bool inverse, const uint32_t* src
 // BabyBearDomain::fft / ifft on a coset (src/math/domain.rs:85-123) with the scaling fused into the passes
 static void test_coset(int log_n, uint64_t batch, uint32_t shift) {
     NttPlan plan;
-    CHECK(build_plan(log_n, plan, latency_plan), "plan %d", log_n);
+    CHECK(build_plan(knobs, log_n, plan, latency_plan), "plan %d", log_n);
     const size_t n = (size_t)1 << log_n;
     std::vector<uint64_t> ref(n * batch), want(n * batch);
     orc_fill_splitmix(ref.data(), n * batch, 0xC05E7ull + log_n);
@@ -191,7 +192,7 @@ static void test_coset(int log_n, uint64_t batch, uint32_t shift) {
 // compact coefficient vector ([n >> lde_log][4]) with the padding implied.
 static void test_ext(int log_n, uint64_t vectors, uint32_t shift, int lde_log = 0) {
     NttPlan plan;
-    CHECK(build_plan(log_n, plan, latency_plan && (log_n == 21 || (log_n == 22 && lde_log))), "plan %d", log_n);   // "Q1": 2^21, and the LDE to 2^22, through their two-pass plans
+    CHECK(build_plan(knobs, log_n, plan, latency_plan && (log_n == 21 || (log_n == 22 && lde_log))), "plan %d", log_n);   // "Q1": 2^21, and the LDE to 2^22, through their two-pass plans
     const size_t n = (size_t)1 << log_n, n_in = n >> lde_log;
     std::vector<uint64_t> ref(4 * n_in * vectors);
     orc_fill_splitmix(ref.data(), ref.size(), 0xE7700ull + (uint64_t)log_n * 131 + (uint64_t)lde_log);
@@ -251,7 +252,7 @@ static void test_field() {
 
 static void test_ntt(int log_n, uint64_t batch, int pattern) {
     NttPlan plan;
-    CHECK(build_plan(log_n, plan, latency_plan), "plan %d", log_n);
+    CHECK(build_plan(knobs, log_n, plan, latency_plan), "plan %d", log_n);
     const size_t n = (size_t)1 << log_n;
     std::vector<uint64_t> ref(n * batch);
     if (pattern == 0) orc_fill_splitmix(ref.data(), n * batch, 0x70796E69ull + ((uint64_t)log_n << 32));
@@ -286,7 +287,7 @@ static void test_ntt(int log_n, uint64_t batch, int pattern) {
 
 static void test_fold(int log_N, int layer, uint32_t shift) {
     NttPlan plan;
-    CHECK(build_plan(log_N, plan), "plan");
+    CHECK(build_plan(knobs, log_N, plan), "plan");
     const size_t N = (size_t)1 << log_N, m = N >> layer, half = m / 2;
     std::vector<uint64_t> evals(m), xs(N), want(half);
     orc_fill_splitmix(evals.data(), m, 77 + layer);
@@ -451,7 +452,7 @@ static void test_merkle_coop() {
 // Low-degree extension: compact input (n >> lde_log words per transform), zero padding implied, coset shift fused
 static void test_lde(int log_n, uint64_t batch, int lde_log, uint32_t shift) {
     NttPlan plan;
-    CHECK(build_plan(log_n, plan, latency_plan), "plan %d", log_n);
+    CHECK(build_plan(knobs, log_n, plan, latency_plan), "plan %d", log_n);
     const uint64_t n = 1ull << log_n, n_in = n >> lde_log;
     std::vector<uint64_t> c64(n_in * batch);
     orc_fill_splitmix(c64.data(), c64.size(), 0x1DE0000ull + (uint64_t)log_n * 64 + (uint64_t)lde_log);
@@ -472,7 +473,7 @@ static void test_lde(int log_n, uint64_t batch, int lde_log, uint32_t shift) {
 // column block, the all-to-all as memcpy, relayout, size-S1 row transforms -- and the mirrored inverse.
 static void emu_slab_pass(const NttPlan& plan, bool inverse, uint32_t* slab, uint64_t cols, uint64_t col_base, const uint32_t* ones) {
     const std::vector<uint32_t>& blob = inverse ? plan.inv : plan.fwd;
-    bool ok = slab_pass(plan, blob.data(), inverse, slab, cols, col_base, ones, [&](auto pass, const PassArgs& a, uint64_t nblocks) {
+    bool ok = slab_pass(knobs, plan, blob.data(), inverse, slab, cols, col_base, ones, [&](auto pass, const PassArgs& a, uint64_t nblocks) {
         using P = decltype(pass);
         std::vector<uint32_t> lds(P::LDS_WORDS, 0xDEADBEEFu);
         for (uint64_t v = 0; v < nblocks; ++v) emu_tile<P>(a, P::tile_order((uint32_t)v, (uint32_t)nblocks), lds.data());
@@ -510,10 +511,10 @@ static bool emu_slab_rows(const NttPlan& big, const NttPlan& sub, bool inverse, 
     sio.dry = true;
     const std::vector<uint32_t>& blob = inverse ? sub.inv : sub.fwd;
     bool ok = sub.npasses >= 2 && rows >= 2 &&
-              for_each_pass<0>(sub, blob.data(), inverse, in, work, out, rows, [](auto, auto, const PassArgs&, uint64_t) {}, CosetTables(), 0, false, &sio);
+              for_each_pass<0>(knobs, sub, blob.data(), inverse, in, work, out, rows, [](auto, auto, const PassArgs&, uint64_t) {}, CosetTables(), 0, false, &sio);
     if (!ok || unsupported) { ++slab_rows_fallback; return false; }
     sio.dry = false;
-    ok = for_each_pass<0>(sub, blob.data(), inverse, in, work, out, rows, [&](auto pass, auto lzc, const PassArgs& a, uint64_t nblocks) {
+    ok = for_each_pass<0>(knobs, sub, blob.data(), inverse, in, work, out, rows, [&](auto pass, auto lzc, const PassArgs& a, uint64_t nblocks) {
         using P = decltype(pass);
         constexpr int LZ = decltype(lzc)::value;
         std::vector<uint32_t> lds(P::LDS_WORDS, 0xDEADBEEFu);
@@ -526,9 +527,9 @@ static bool emu_slab_rows(const NttPlan& big, const NttPlan& sub, bool inverse, 
 
 static void test_slab(int log_n, uint64_t G) {
     NttPlan plan, sub;
-    CHECK(build_plan(log_n, plan), "plan %d", log_n);
+    CHECK(build_plan(knobs, log_n, plan), "plan %d", log_n);
     const uint64_t n = 1ull << log_n, m1 = 1ull << plan.pass[0].log_m, s1 = n / m1;
-    CHECK(build_plan(log_n - plan.pass[0].log_m, sub), "sub plan");
+    CHECK(build_plan(knobs, log_n - plan.pass[0].log_m, sub), "sub plan");
     const uint64_t W = s1 / G, R = m1 / G;
     std::vector<uint64_t> x(n), want(n);
     orc_fill_splitmix(x.data(), n, 0x51AB0000ull + (uint64_t)log_n * 16 + G);
@@ -586,7 +587,7 @@ static DomainArgs emu_domain(const NttPlan& plan, int log_m, uint32_t shift) {
 }
 static void test_prover_steps(int log_N, int log_blowup, uint32_t shift) {
     NttPlan plan;
-    CHECK(build_plan(log_N, plan), "plan");
+    CHECK(build_plan(knobs, log_N, plan), "plan");
     const size_t N = (size_t)1 << log_N, n = N >> log_blowup, B = (size_t)1 << log_blowup;
     std::vector<uint64_t> lde(N), cw(N), qw(N), dw(N);
     orc_fill_splitmix(lde.data(), N, 0xF1B0 + log_N);
@@ -721,7 +722,7 @@ int main(int argc, char** argv) {
         test_coset(log_n, log_n <= 10 ? 5 : 2, 7);  // COSET_SHIFT = 7, src/fibonacci.rs:16
         if (log_n >= 11) {                          // every zero fraction the first pass of this plan supports
             NttPlan probe;
-            build_plan(log_n, probe);
+            build_plan(knobs, log_n, probe);
             for (int z = 1; z <= probe.pass[0].log_m; ++z) test_lde(log_n, z == 1 ? 3 : 1, z, z & 1 ? 7u : 1u);
         }
         if (log_n >= 1) {                           // Ext (AoS) transforms: one vector, a ragged few, plain and coset
@@ -729,7 +730,7 @@ int main(int argc, char** argv) {
             test_ext(log_n, log_n <= 10 ? 11 : 2, 7);
             if (log_n >= 11) {
                 NttPlan probe;
-                build_plan(log_n, probe);
+                build_plan(knobs, log_n, probe);
                 for (int z = 1; z <= probe.pass[0].log_m; z += 2) test_ext(log_n, 1, 7, z);
             }
         }
@@ -739,7 +740,7 @@ int main(int argc, char** argv) {
     for (int i = 2; i < argc; ++i) {                // extra sizes "LOG" or "LOGxBATCH" (2-pass 2^20, 3-pass 2^21.., wide tiles)
         const char* xb = std::strchr(argv[i], 'x');
         if (argv[i][0] == 'p') {                    // "pN": launches of <= 2^N 32-wide tiles take the three-step shapes from here on (-1: never)
-            pass3_max_log_tiles32() = std::atoi(argv[i] + 1);
+            knobs.p3_tiles = std::atoi(argv[i] + 1);
             continue;
         }
         if (argv[i][0] == 'Q') {
@@ -755,7 +756,7 @@ int main(int argc, char** argv) {
             continue;
         }
         if (argv[i][0] == 'w') {                    // "wN": launches of >= 2^N 32-wide tiles take the 64-wide shapes of the 128/256-point passes
-            wide_min_log_tiles32() = std::atoi(argv[i] + 1);
+            knobs.wide_tiles = std::atoi(argv[i] + 1);
             continue;
         }
         if (argv[i][0] == 'l') {                    // "lLOGxZ": low-degree extension of 2^(LOG-Z) coefficients to 2^LOG points
@@ -791,7 +792,7 @@ int main(int argc, char** argv) {
         if (log_n > max_log) continue;
         for (uint64_t G : {1, 2, 4}) {
             NttPlan probe;
-            build_plan(log_n, probe);
+            build_plan(knobs, log_n, probe);
             if (((1ull << log_n) >> probe.pass[0].log_m) / G < 32) continue;
             test_slab(log_n, G);
         }

@@ -164,6 +164,40 @@ def test_plain_2p22_keeps_the_three_pass_plan_and_lone_transforms_the_latency_sh
     assert ctx13.passes == 2 and ctx13.passes_for(1) == 2 and ctx13.passes_for(1 << 12) == 1    # the single-sweep kernel from 2^25 elements
 
 
+def test_launches_enqueued_equal_passes_for_either_side_of_every_route_gate(ta):
+    """What ties the route function (toyni_amd/csrc/ntt_route.hpp, table-checked on the CPU by tests/test_route_table.py) to what
+    the launcher enqueues: the launch records of the measurement build for ONE forward transform call against passes_for(batch),
+    one batch below and at the row sweeps' threshold (2^11), the LDS sweep's (2^13: 2^25 elements), and the plan choices of
+    2^21 / 2^22; the last call's first and last transform against the oracle."""
+    import os
+    if any(k.startswith("TOYNI_") and k not in ("TOYNI_LAUNCH_LOG", "TOYNI_FUZZ_SEED", "TOYNI_FUZZ_CASES") for k in os.environ):
+        pytest.skip("the default dispatch's plan choices are asserted only without dispatch knobs (tools/knob_soak.sh)")
+    from test_gpu_parity import _run_on_measurement_build
+    code = (
+        "import numpy as np, oracle, toyni_amd\n"
+        "from test_gpu_parity import DevBuf\n"
+        "want = {(11, 2047): 2, (11, 2048): 1, (13, 4095): 2, (13, 4096): 1, (21, 1): 2, (21, 4): 2, (22, 2): 2, (22, 3): 3}\n"
+        "buf = DevBuf(toyni_amd, 4 << 25, guard=4 << 22)   # 128 MiB: 4096 x 2^13; the guards one 2^22 transform\n"
+        "for (log_n, batch), launches in want.items():\n"
+        "    n = 1 << log_n\n"
+        "    ctx = toyni_amd.NttContext(n)\n"
+        "    x = np.random.default_rng(log_n * 5000 + batch).integers(0, oracle.P, size=n * batch, dtype=np.uint32)\n"
+        "    buf.upload(x)\n"
+        "    ctx.timing(True)\n"
+        "    ctx.run_device(buf.ptr, buf.ptr, batch, False)\n"
+        "    got = sum(ctx.read_timing()['launches']['forward'])\n"
+        "    ctx.timing(False)\n"
+        "    print(log_n, batch, 'launches', got, 'passes_for', ctx.passes_for(batch), flush=True)\n"
+        "    assert got == ctx.passes_for(batch) == launches, (log_n, batch, got, ctx.passes_for(batch), launches)\n"
+        "y = buf.download(np.uint32, x.size)\n"
+        "for t in (0, batch - 1):\n"
+        "    assert (y[t * n:(t + 1) * n] == oracle.ntt(x[t * n:(t + 1) * n].astype(np.uint64))).all(), t\n"
+        "buf.free()\n"
+        "print('LAUNCHES OK')\n")
+    res = _run_on_measurement_build(code)
+    assert res.returncode == 0 and "LAUNCHES OK" in res.stdout, res.stdout[-1500:] + res.stderr[-3000:]
+
+
 def test_random_shapes_on_the_two_pass_plans(ta):
     """Seeded differential fuzz over the sizes with a second plan (n = 2^21, 2^22): batches either side of the 2^7-tile gate, both
     directions, coset shifts, in place / out of place, chunked launches, low-degree extensions of every blow-up, Ext vectors at 2^21.

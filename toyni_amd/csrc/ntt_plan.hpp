@@ -5,13 +5,13 @@
 // words) and one two-level table per pass boundary (<= 24 K words), all u32 in Montgomery form.
 // Plain C++ (shared with tests/emu).
 #pragma once
-#include <cstdlib>
 #include <stdint.h>
 #include <type_traits>
 #include <vector>
 
 #include "bb_field.hpp"
 #include "ntt_kernels.hpp"
+#include "ntt_route.hpp"
 
 namespace toyni {
 
@@ -44,36 +44,13 @@ struct NttPlan {
     std::vector<uint32_t> fwd, inv;     // table blobs, Montgomery form
 };
 
-// latency = true: the SECOND plan of n = 2^21 / 2^22, two passes with a 2048-point three-step pass.  Rounds 2-4: 4-wide latency tiles
-// only -- one launch fewer for a lone transform -- while streaming launches kept the three-pass split below.  Round 5: the 2048-point
-// pass also has a STREAMING shape (16-wide tiles, 32 elements per thread), so n = 2^21 runs this plan for launches of every size
-// (has_stream2_plan), n = 2^22 for lone transforms and for its low-degree extensions (toyni_hip.hip: use_two_pass_plan)
-// (n = 2^23 / 2^24 as 4096-point three-step passes were built and measured too: 54.6 against 50.7 us and 124 against 88 us for the
-// three-pass plan -- a 4096 x 4 tile is one 1024-thread workgroup per CU with 16-byte row segments; not kept)
-inline bool has_latency_plan(int log_n) { return log_n == 21 || log_n == 22; }
-// Uneven splits: which pass gets the extra stage.  A column pass also applies the inter-pass twiddle and reads strided; the closing
-// row pass does neither -- so the larger factor goes LAST (experiment switch TOYNI_SPLIT_SMALL_FIRST=0: first, as in round 1).
-inline bool& split_small_first() {
-    static bool v = [] { const char* env = std::getenv("TOYNI_SPLIT_SMALL_FIRST"); return env ? env[0] != '0' : true; }();
-    return v;
-}
-// element `idx` of a comma-separated integer list in the environment (0 when absent)
-inline int plan_env_triple(const char* name, int idx) {
-    const char* env = std::getenv(name);
-    if (!env) return 0;
-    for (int i = 0; i < idx; ++i) {
-        while (*env && *env != ',') ++env;
-        if (!*env) return 0;
-        ++env;
-    }
-    return std::atoi(env);
-}
-inline void split_passes(int log_n, int& npasses, int (&logm)[MAX_PASSES], bool latency = false) {
+// How log2(n) is split into passes.  latency: the second, two-pass plan of n = 2^21 / 2^22 (has_latency_plan, ntt_route.hpp)
+inline void split_passes(const LaunchKnobs& k, int log_n, int& npasses, int (&logm)[MAX_PASSES], bool latency = false) {
     // (the larger factor LAST, as in the two-pass plans below: at n = 2^21 the 2048-point pass is then the closing row pass, which has a
     // streaming form -- contiguous rows in, 64-byte segments out -- besides the 4-wide latency form)
     if (latency && has_latency_plan(log_n)) { npasses = 2; logm[0] = log_n / 2; logm[1] = (log_n + 1) / 2; logm[2] = 0; return; }
     if (log_n <= 10) { npasses = 1; logm[0] = log_n; logm[1] = logm[2] = 0; return; }
-    const bool small_first = split_small_first();
+    const bool small_first = k.split_small_first;
     if (log_n <= 20) {
         npasses = 2;
         const int hi = (log_n + 1) / 2, lo = log_n / 2;
@@ -88,9 +65,7 @@ inline void split_passes(int log_n, int& npasses, int (&logm)[MAX_PASSES], bool 
     logm[0] = small_first ? c : a;
     logm[1] = b;
     logm[2] = small_first ? a : c;
-    // experiment switch TOYNI_SPLIT3="a,b,c": that split for the size a + b + c (column shapes exist for 6..10 stage bits, closing row
-    // shapes for 5..10); the A/B of profiles/r05_ab_split3.txt
-    static const int forced[3] = {plan_env_triple("TOYNI_SPLIT3", 0), plan_env_triple("TOYNI_SPLIT3", 1), plan_env_triple("TOYNI_SPLIT3", 2)};
+    const int (&forced)[3] = k.split3;   // experiment switch TOYNI_SPLIT3
     if (forced[0] + forced[1] + forced[2] == log_n && forced[0] >= 6 && forced[0] <= 10 && forced[1] >= 6 && forced[1] <= 10 && forced[2] >= 5 &&
         forced[2] <= 10) {
         logm[0] = forced[0]; logm[1] = forced[1]; logm[2] = forced[2];
@@ -148,11 +123,11 @@ inline void append_two_level(std::vector<uint32_t>& blob, int log_l, uint32_t w,
     }
 }
 
-inline bool build_plan(int log_n, NttPlan& plan, bool latency = false) {
+inline bool build_plan(const LaunchKnobs& k, int log_n, NttPlan& plan, bool latency = false) {
     if (log_n < 0 || log_n > MAX_LOG_N) return false;  // cuda/ntt_kernel.cu:217-220
     plan.log_n = log_n;
     int logm[MAX_PASSES];
-    split_passes(log_n, plan.npasses, logm, latency);
+    split_passes(k, log_n, plan.npasses, logm, latency);
     const uint32_t w_n = bb_root_of_unity_host((uint32_t)log_n);      // cuda/ntt_kernel.cu:222-223
     const uint32_t w_n_inv = bb_pow_host(w_n, (1ull << log_n) - 1);   // omega^(n-1), src/ntt.rs:59
     const uint32_t n_inv = bb_inv_host((uint32_t)((1ull << log_n) % BB_P));  // src/ntt.rs:62
@@ -215,6 +190,7 @@ inline bool build_plan(int log_n, NttPlan& plan, bool latency = false) {
     }
     return true;
 }
+inline bool build_plan(int log_n, NttPlan& plan, bool latency = false) { return build_plan(launch_knobs(), log_n, plan, latency); }   // the process's knobs
 
 // the order-(n >> s) subgroup inside the plan's domain table, on the blob at `tables` (fwd or inv; host or device copy)
 inline SubDomain sub_domain(const NttPlan& plan, const uint32_t* tables, int s) {
@@ -236,28 +212,7 @@ inline SubDomain sub_domain(const NttPlan& plan, const uint32_t* tables, int s) 
 // cover the chip the narrower variants (16 / 8 wide) are used -- the data is cache-resident at that size anyway.
 // `log_tiles32` = log2 of the number of 32-wide tiles the launch would have.
 // nt: the non-temporal variant of the same shape (streaming launches, see ld32 / st32).
-// Launches of at most 2^pass3_max_log_tiles32() 32-wide tiles (a single transform, or a handful: the data is cache-resident
-// and the chip is far from full) run the three-step shapes `Pass3` with 4-wide tiles instead: 8x the workgroups of the 32-wide
-// shape and half the serial work per wave.  -1 = never.  (A variable so that tests/emu can step both executors and the library
-// can take TOYNI_P3_TILES from the environment.)
-// The three dispatch knobs below take their value from the environment ONCE, in their thread-safe static initialiser; the library
-// never writes them afterwards (tests/emu does, to step both executors).
-inline int plan_env_int(const char* name, int dflt) {
-    const char* env = std::getenv(name);
-    return env ? std::atoi(env) : dflt;
-}
-inline int& pass3_max_log_tiles32() {
-    static int v = plan_env_int("TOYNI_P3_TILES", 6);   // -1: never the three-step shapes
-    return v;
-}
-
-// launches that take the two-pass latency plan of n = 2^21 / 2^22 (has_latency_plan): those whose first pass has at most this
-// many (log2) 32-wide tiles' worth of columns
-inline int& lat_max_log_tiles32() {
-    static int v = plan_env_int("TOYNI_LAT_TILES", 7);  // -1: never the two-pass latency plans
-    return v;
-}
-
+// The tile-count thresholds (k.p3_tiles, k.wide_tiles, k.s3_tiles) are LaunchKnobs, ntt_route.hpp.
 // experiment switches (compile time): tile width (log2) of the wide variants of the 128-point and the 512-point passes
 #ifndef TOYNI_WIDE_43
 #define TOYNI_WIDE_43 6
@@ -265,38 +220,21 @@ inline int& lat_max_log_tiles32() {
 #ifndef TOYNI_WIDE_54
 #define TOYNI_WIDE_54 6
 #endif
-inline int& wide_min_log_tiles32() {
-    static int v = plan_env_int("TOYNI_WIDE_TILES", 12);  // 99: never the 64-wide shapes
-    return v;
-}
-// launches of at least this many (log2) 32-wide tiles run a 2048-point pass in its streaming three-step shape (16-wide tiles, 32
-// elements per thread, ntt_pass3s_kernel) and n = 2^21 as the two sweeps of its "latency" plan; 99 = never (the three-pass plan)
-inline int& stream3_min_log_tiles32() {
-    static int v = plan_env_int("TOYNI_S3_TILES", 7);
-    return v;
-}
-// Sizes whose two-pass plan beats the three-pass one on streaming launches.  n = 2^21: 1024-point column pass + 2048-point closing
-// pass, 1.05 against 1.32 ms per 2^28 elements.  n = 2^22 as two 2048-point passes was built and measured too and is NOT taken
-// (profiles/r05_ab_stream3.txt): 1.28-1.33 ms against 1.24-1.27 for 7/7/8 -- a 16-column tile means 64-byte row segments on both
-// sides of the column pass, and with the inter-pass twiddle that pass takes 0.71 ms where the closing pass takes 0.57.  What the
-// 16-wide column shape is kept for is the FIRST pass of a low-degree extension of n = 2^22 (it reads 2^-blow-up of its input:
-// 0.95 against 1.21 ms for 64 x 2^17 -> 2^22), so only its zero-fraction variants are instantiated (dispatch_pass_lz).
-inline bool has_stream2_plan(int log_n) { return log_n == 21; }
 
 // LQ > 0: the interleaved (Ext, AoS) variants: the same table (a lone Ext vector counts as four transforms' worth of tiles), without
 // the 8-wide two-step shapes and the 2048-point latency and column shapes (the streaming 2048-point CLOSING pass has its interleaved form).
 template <int LQ = 0, class F>
-inline bool dispatch_pass(int kind, int log_m, int log_tiles32, F&& f, bool nt = false) {
+inline bool dispatch_pass(const LaunchKnobs& k, int kind, int log_m, int log_tiles32, F&& f, bool nt = false) {
     // measured crossover (profiles/r02_latency.txt): 2^6 32-wide tiles for the 1024-point shapes, 2^7 for the 512-point and 2^8
     // for the 256-point ones (8 elements per thread: lighter, they win up to larger launches)
     // 2048-point passes exist only in the two-pass plans of n = 2^21 / 2^22 and only as three-step shapes (4-wide latency tiles here; the
     // 16-wide streaming closing pass above)
     // the streaming 2048-point closing pass (base and interleaved form; a lone Ext vector is already 2^7 32-wide tiles' worth at n = 2^21)
-    if (log_m == 11 && kind == KIND_ROW_T && log_tiles32 >= stream3_min_log_tiles32()) {
+    if (log_m == 11 && kind == KIND_ROW_T && log_tiles32 >= k.s3_tiles) {
         if (nt) f(Pass3<KIND_ROW_T, 5, 3, 3, 4, true, LQ>{}); else f(Pass3<KIND_ROW_T, 5, 3, 3, 4, false, LQ>{});
         return true;
     }
-    if ((LQ == 0 && log_m == 11) || (pass3_max_log_tiles32() >= 0 && log_m >= 8 && log_m <= 10 && log_tiles32 <= pass3_max_log_tiles32() + (10 - log_m))) {
+    if ((LQ == 0 && log_m == 11) || (k.p3_tiles >= 0 && log_m >= 8 && log_m <= 10 && log_tiles32 <= k.p3_tiles + (10 - log_m))) {
 #define TOYNI_PASS3_CASE(K, A, B, D) if (kind == K && log_m == (A) + (B) + (D)) { f(Pass3<K, A, B, D, 2, false, LQ>{}); return true; }
         if constexpr (LQ == 0) {   // 2048-point passes exist only in the base form's latency plans of n = 2^21 / 2^22
             TOYNI_PASS3_CASE(KIND_COL, 4, 4, 3)
@@ -324,13 +262,13 @@ inline bool dispatch_pass(int kind, int log_m, int log_tiles32, F&& f, bool nt =
     }
     // The 128-, 256- and 512-point passes (three-pass plans n >= 2^21, two-pass plans up to 2^19) are memory-bound, and the strided
     // pattern moves more with 256-byte row segments than with 128-byte ones (tools/membench.hip: 4.85 against 4.4 TB/s): large
-    // launches take 64-wide tiles (wide_min_log_tiles32(): launches of at least that many 32-wide tiles; a huge value = never).
+    // launches take 64-wide tiles (k.wide_tiles: launches of at least that many 32-wide tiles; a huge value = never).
     // Measured (profiles/r02_ab_wide.txt): +7.7 % at 64 x 2^24, +6 % at 2^21 / 2^22, +5.4 % at 2^27, +3.8 % at 2^18; 128-wide tiles for
     // the 128-point passes add another 0.7-1.5 % at 2^21 / 2^22 and lose 0.3 % at 2^13 / 2^14 (not taken).  The 1024-point passes
     // of n = 2^20 cannot widen: a 64 x 1024 tile is 256 KiB.
 #define TOYNI_PASS_CASE_WIDE(K, A, B, LCW)                                            \
     if (kind == K && log_m == (A) + (B)) {                                             \
-        if (log_tiles32 >= wide_min_log_tiles32() + ((LCW) - 6)) TOYNI_PASS_GO(K, A, B, LCW); \
+        if (log_tiles32 >= k.wide_tiles + ((LCW) - 6)) TOYNI_PASS_GO(K, A, B, LCW); \
         else TOYNI_PASS_GO(K, A, B, 5);                                                \
         return true;                                                                   \
     }
@@ -378,7 +316,7 @@ inline bool dispatch_pass(int kind, int log_m, int log_tiles32, F&& f, bool nt =
 // First pass of a low-degree extension (zero-padded input, PassArgs::in_prefix_log): the same column shapes with the
 // zero fraction as a compile-time parameter, f(Pass{}, std::integral_constant<int, LZ>{}), LZ = 1..5.
 template <int LQ = 0, class F>
-inline bool dispatch_pass_lz(int log_m, int log_tiles32, int lz, F&& f) {
+inline bool dispatch_pass_lz(const LaunchKnobs& k, int log_m, int log_tiles32, int lz, F&& f) {
 #define TOYNI_LZ_CASES(PASS)                                                                 \
     switch (lz) {                                                                            \
         case 1: f(PASS{}, std::integral_constant<int, 1>{}); return true;                    \
@@ -390,11 +328,11 @@ inline bool dispatch_pass_lz(int log_m, int log_tiles32, int lz, F&& f) {
     }
 #define TOYNI_COMMA ,
     // (the interleaved form too: the LDE of Ext vectors to 2^22 points -- a lone vector is 2^8 32-wide tiles' worth)
-    if (log_m == 11 && log_tiles32 >= stream3_min_log_tiles32()) { TOYNI_LZ_CASES(Pass3<KIND_COL TOYNI_COMMA 5 TOYNI_COMMA 3 TOYNI_COMMA 3 TOYNI_COMMA 4 TOYNI_COMMA false TOYNI_COMMA LQ>) }
+    if (log_m == 11 && log_tiles32 >= k.s3_tiles) { TOYNI_LZ_CASES(Pass3<KIND_COL TOYNI_COMMA 5 TOYNI_COMMA 3 TOYNI_COMMA 3 TOYNI_COMMA 4 TOYNI_COMMA false TOYNI_COMMA LQ>) }
     if constexpr (LQ == 0) {
         if (log_m == 11) { TOYNI_LZ_CASES(Pass3<KIND_COL TOYNI_COMMA 4 TOYNI_COMMA 4 TOYNI_COMMA 3 TOYNI_COMMA 2>) }
     }
-    if (pass3_max_log_tiles32() >= 0 && log_m >= 8 && log_m <= 10 && log_tiles32 <= pass3_max_log_tiles32() + (10 - log_m)) {
+    if (k.p3_tiles >= 0 && log_m >= 8 && log_m <= 10 && log_tiles32 <= k.p3_tiles + (10 - log_m)) {
         if (log_m == 8) { TOYNI_LZ_CASES(Pass3<KIND_COL TOYNI_COMMA 3 TOYNI_COMMA 3 TOYNI_COMMA 2 TOYNI_COMMA 2 TOYNI_COMMA false TOYNI_COMMA LQ>) }
         if (log_m == 9) { TOYNI_LZ_CASES(Pass3<KIND_COL TOYNI_COMMA 3 TOYNI_COMMA 3 TOYNI_COMMA 3 TOYNI_COMMA 2 TOYNI_COMMA false TOYNI_COMMA LQ>) }
         if constexpr (LQ == 0) {
@@ -460,7 +398,7 @@ template <class P> constexpr bool slab_variant_exists() {
 }
 
 template <int LQ = 0, class Launch>
-inline bool for_each_pass(const NttPlan& plan, const uint32_t* tables, bool inverse, const uint32_t* src,
+inline bool for_each_pass(const LaunchKnobs& k, const NttPlan& plan, const uint32_t* tables, bool inverse, const uint32_t* src,
                           uint32_t* work, uint32_t* dst, uint64_t batch, Launch&& launch, const CosetTables& cs = CosetTables(),
                           int lde_log = 0, bool nt = false, const SlabIo* sio = nullptr) {
     if (plan.log_n == 0 || batch == 0) return true;  // n = 1: identity
@@ -545,9 +483,9 @@ inline bool for_each_pass(const NttPlan& plan, const uint32_t* tables, bool inve
         bool ok;
         // the pass that touches the pieces layout of a slab launch takes its 32-wide plain shape (the only ones with a SLAB variant)
         const bool slab_special = sio && ((!inverse && p == 0) || (inverse && p == plan.npasses - 1));
-        if (slab_special && log_tiles32 >= wide_min_log_tiles32()) log_tiles32 = wide_min_log_tiles32() - 1;
-        if (p == 0 && lde_log) ok = dispatch_pass_lz<LQ>(pp.log_m, log_tiles32, lde_log < 5 ? lde_log : 5, body);
-        else ok = dispatch_pass<LQ>(pp.kind, pp.log_m, log_tiles32, [&](auto pass) { body(pass, std::integral_constant<int, 0>{}); }, nt && !slab_special);
+        if (slab_special && log_tiles32 >= k.wide_tiles) log_tiles32 = k.wide_tiles - 1;
+        if (p == 0 && lde_log) ok = dispatch_pass_lz<LQ>(k, pp.log_m, log_tiles32, lde_log < 5 ? lde_log : 5, body);
+        else ok = dispatch_pass<LQ>(k, pp.kind, pp.log_m, log_tiles32, [&](auto pass) { body(pass, std::integral_constant<int, 0>{}); }, nt && !slab_special);
         if (!ok) return false;
     }
     return true;
@@ -624,7 +562,7 @@ inline bool row2048_transform(const NttPlan& plan, const uint32_t* tables, bool 
 //             max(2^lowbits, n >> lowbits) words, standing in for the inter-pass twiddle table.
 // launch(PassType{}, args, nblocks).
 template <class Launch>
-inline bool slab_pass(const NttPlan& plan, const uint32_t* tables, bool inverse, uint32_t* slab, uint64_t cols_local,
+inline bool slab_pass(const LaunchKnobs& k, const NttPlan& plan, const uint32_t* tables, bool inverse, uint32_t* slab, uint64_t cols_local,
                       uint64_t col_base, const uint32_t* ones, Launch&& launch) {
     if (plan.npasses < 2 || cols_local < 32 || (cols_local & (cols_local - 1))) return false;
     const PassPlan& pp = plan.pass[0];
@@ -650,8 +588,8 @@ inline bool slab_pass(const NttPlan& plan, const uint32_t* tables, bool inverse,
         a.scale = to_mont_host(bb_inv_host((uint32_t)(1u << pp.log_m)));
     }
     int log_tiles32 = log_c - 5;
-    if (log_c < 6 && log_tiles32 >= wide_min_log_tiles32()) log_tiles32 = wide_min_log_tiles32() - 1;  // a 32-column slab cannot hold a 64-wide tile
-    return dispatch_pass(KIND_COL, pp.log_m, log_tiles32, [&](auto pass) {
+    if (log_c < 6 && log_tiles32 >= k.wide_tiles) log_tiles32 = k.wide_tiles - 1;  // a 32-column slab cannot hold a 64-wide tile
+    return dispatch_pass(k, KIND_COL, pp.log_m, log_tiles32, [&](auto pass) {
         using P = decltype(pass);
         launch(pass, a, cols_local / P::C);
     });
