@@ -310,7 +310,9 @@ int toyni_merkle_open_rows_device(const uint8_t* d_levels, size_t n, const uint3
  *     src/transcript.rs:34-40) and there is one common denominator x - z (src/fibonacci.rs:193-196).  With 3d the sequence
  *         batched inverse transform -> toyni_lde_device(batch = w) -> toyni_merkle_commit_rows_device -> toyni_poly_eval_batch_device
  *         -> toyni_deep_combine_device -> toyni_fri_commit_phase_device -> toyni_merkle_open_rows_device
- *     stays on the device; the AIR's constraint evaluation between the commitment and the quotient is 3f.
+ *     stays on the device; the AIR's constraint evaluation between the commitment and the quotient is 3f.  A staged AIR adds one stage
+ *     after the main columns' commitment: the per-row terms from a 3f program at log_blowup = 0 -> toyni_column_scan_device (3g) -> the
+ *     accumulator columns through the same inverse transform, toyni_lde_device and toyni_merkle_commit_rows_device as a second matrix.
  *     Both calls are asynchronous on `stream`, take packed-u32 canonical residues and write canonical residues.  Device pointers are
  *     4-byte aligned.  `points` and `terms` are host arrays that the caller may reuse as soon as the call returns.  Both calls may use the
  *     context's per-stream intermediate buffer (calls on one stream run in order; use one stream per concurrent call).
@@ -412,6 +414,51 @@ int toyni_air_program_info(const toyni_air_program* prog, toyni_air_info* info);
 int toyni_air_quotient_device(toyni_ntt_ctx* ctx, const toyni_air_program* prog, const toyni_air_matrix* mats, size_t nmats,
                               unsigned log_blowup, uint32_t shift, const uint32_t* weights, size_t nweights, uint32_t* d_c_out,
                               uint32_t* d_q_out, int accumulate, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 3g. Accumulator columns: the auxiliary columns of a staged AIR, built from committed columns and a challenge gamma --
+ *         the running product of a permutation argument   z_{i+1} = z_i * (gamma + a_i) / (gamma + b_i)
+ *         the running sum of a LogUp lookup               s_{i+1} = s_i + 1 / (gamma + v_i) - m_i / (gamma + t_i)
+ *     (src/ext.rs:1-8 names "lookup/permutation challenges" and "accumulators" as what a STARK over this field carries).  The per-row
+ *     numerator and denominator of such a term come from 3f: a program with undivided EMITs, run with log_blowup = 0 and shift = 1
+ *     on a context of the trace length, weights (1, 0) and (0, 1).  What is new here is the inversion of n values that are data, and
+ *     the one dependency from row i to row i + 1 in this library.  Inside the protocol shape of 3e / 3f: base-field challenges and
+ *     base-field columns.
+ *     Asynchronous on `stream`; packed-u32 canonical residues in and out.  The context lends its device, its lock and its per-stream
+ *     intermediate buffer (2 words per tile and column); n is NOT tied to the context's size.
+ *     Size: 1 <= n <= 2^27, any n, not only powers of two.  batch == 0 or n == 0 succeeds and writes nothing.
+ *     Exactness: + and * mod p are associative and commutative, so every evaluation order gives the same words: the result is the
+ *     exact residue, bit for bit, at every launch shape.
+ *     In place: d_out may be exactly d_num or exactly d_den, with the same stride.  Any other overlap is the caller's error.
+ *     Refused before anything is enqueued, the outputs untouched and the context not touched -- TOYNI_E_NULL for a null ctx, d_out or
+ *     init, or both operands null; TOYNI_E_RANGE for: an unknown op; n > 2^27; a stride < n with batch > 1; batch >= 2^16; an init
+ *     value >= p; a device pointer that is not 4-byte aligned.
+ *     Loads and stores: a column whose first word is 16-byte aligned is read and written 16 bytes at a time, any other by word
+ *     accesses; the result is the same.
+ *     Three launches, each ordered after the last by the stream -- per-tile aggregates on a grid of (tile, column); one workgroup per
+ *     column scanning that column's aggregates; the scan inside every tile on the same grid -- and a single launch, grid = the columns,
+ *     for n <= one tile.  No workgroup waits for another.  The seeds travel inside the kernel arguments, 64 columns to a launch
+ *     sequence, so a call on a warm context only enqueues kernels and can be captured into a HIP graph (with the caveat of section 4).
+ * ---------------------------------------------------------------------------------------------- */
+#define TOYNI_SCAN_SUM 0
+#define TOYNI_SCAN_PRODUCT 1
+size_t toyni_column_scan_tile(void);      /* elements one workgroup owns (a power of two): n <= this takes the single launch */
+/* out[i] = in[i]^-1, and 0 where in[i] = 0 (the rule of XINV / toyni_deep_combine_device).  *d_zero_count (may be NULL) = number of
+ * zeros met (cleared by a stream-ordered fill ahead of the kernel).  d_out == d_in allowed.  No context: the current device.
+ * One Fermat inversion per 8 values (Montgomery's trick).  TOYNI_E_NULL for a null d_in or d_out; TOYNI_E_RANGE for count > 2^32 or a
+ * pointer that is not 4-byte aligned.  count == 0 succeeds (and clears the count). */
+int toyni_batch_inverse_device(const uint32_t* d_in, uint32_t* d_out, size_t count, uint32_t* d_zero_count, void* stream);
+/* For each of `batch` columns b (column b of an operand starts at ptr + b * its stride; strides >= n), with
+ *   term_i = num_i / den_i   (d_num == NULL: 1 / den_i;  d_den == NULL: num_i;  den_i == 0: term_i = 0 and the zero is counted)
+ * the EXCLUSIVE running value, which is what an accumulator column is:
+ *   out[0] = init[b];  out[i] = out[i-1] (+ or *) term_{i-1},  0 < i < n
+ *   d_totals[2b] = out[n-1] (+ or *) term_{n-1}   (the wrap-around value: a valid argument has it equal to init[b])
+ *   d_totals[2b+1] = zero denominators met in column b.
+ * init: host array of `batch` canonical residues, reusable on return.  d_totals may be NULL.  The words between n and the stride of
+ * a column are neither read nor written. */
+int toyni_column_scan_device(toyni_ntt_ctx* ctx, const uint32_t* d_num, size_t num_stride, const uint32_t* d_den, size_t den_stride,
+                             uint32_t* d_out, size_t out_stride, size_t n, size_t batch, int op, const uint32_t* init,
+                             uint32_t* d_totals, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:

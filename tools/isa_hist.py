@@ -3,7 +3,8 @@
     tools/isa_hist.py build/toyni.s <symbol substring> [--loop] [--without REGEX]
 Prints VALU / SALU / VMEM / LDS counts per mnemonic, weighted by the measured issue cost of profiles/r02_microbench.txt.
 --loop restricts the count to the kernel's largest inner loop (the blocks the listing marks "Inner Loop Header" / "in Loop: Header=");
---without drops every basic block of it that holds an instruction matching REGEX (a path the case of interest does not take)."""
+--without drops every basic block of it that holds an instruction matching REGEX (a path the case of interest does not take);
+without --loop it filters the basic blocks of the whole kernel (a kernel that is one straight line with a few uniform branches)."""
 import collections
 import re
 import sys
@@ -46,6 +47,19 @@ if "--loop" in sys.argv:   # the largest inner loop
         rx = re.compile(sys.argv[sys.argv.index("--without") + 1])
         split = [b for b in split if not any(rx.search(l) for l in b)]
     body = [l for b in split for l in b]
+elif "--without" in sys.argv:   # a kernel without a loop (the scan kernels): the same filter over the basic blocks of the whole body
+    rx = re.compile(sys.argv[sys.argv.index("--without") + 1])
+    blocks, cur = [], []
+    for l in body:
+        if re.match(r"\.LBB\d+_\d+:", l) and cur:
+            blocks.append(cur)
+            cur = []
+        cur.append(l)
+        if re.match(r"\s+s_c?branch", l):
+            blocks.append(cur)
+            cur = []
+    blocks.append(cur)
+    body = [l for b in blocks if not any(rx.search(l) for l in b) for l in b]
 # cost model (cycles per wave-instruction per SIMD at >= 2 waves / SIMD), profiles/r02_microbench.txt
 FAST = {"v_add_u32", "v_sub_u32", "v_subrev_u32", "v_xor_b32", "v_and_b32", "v_or_b32", "v_mov_b32", "v_lshlrev_b32", "v_lshrrev_b32", "v_add_f32", "v_mul_f32"}
 hist = collections.Counter()

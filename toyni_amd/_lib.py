@@ -120,6 +120,11 @@ SIGNATURES = {
     "toyni_air_program_info": (c_int, [c_void_p, c_void_p]),
     "toyni_air_quotient_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, ctypes.c_uint, c_u32, c_void_p, c_size, c_void_p, c_void_p, c_int,
                                           c_void_p]),
+    # section 3g
+    "toyni_column_scan_tile": (c_size, []),
+    "toyni_batch_inverse_device": (c_int, [c_void_p, c_void_p, c_size, c_void_p, c_void_p]),
+    "toyni_column_scan_device": (c_int, [c_void_p, c_void_p, c_size, c_void_p, c_size, c_void_p, c_size, c_size, c_size, c_int, c_void_p,
+                                         c_void_p, c_void_p]),
     # section 3c
     "toyni_fri_fold_commit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

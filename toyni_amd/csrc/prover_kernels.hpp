@@ -373,6 +373,160 @@ TOYNI_HD void air_eval_group(const AirArgs& a, const uint32_t* weights, uint32_t
     for (int j = 0; j < K; ++j) q[j] = a.divides ? bb_add(mont_mul(c[j], zhR[j]), undiv[j]) : undiv[j];
 }
 
+// ---- accumulator columns: a running sum or product along a column (include/toyni_hip.h 3g) ----
+//   term_i = num_i / den_i (0 where den_i = 0),  out[0] = init,  out[i] = out[i-1] o term_{i-1},  o = + or *
+// The only dependency from row to row in this library.  + and * mod p are associative and commutative, so the column is cut into
+// tiles of SCAN_TILE elements and every partial result is exact whatever the order: (1) one aggregate and one zero count per tile,
+// (2) an exclusive scan of a column's aggregates by one workgroup, (3) the scan inside each tile on top of the tile's prefix.
+// Each launch is ordered after the last by the stream; no workgroup ever waits for another.
+// Sums run on plain residues.  Products run on MONTGOMERY forms (identity R, one mont_mul per step) and are converted when stored.
+constexpr uint32_t SCAN_SUM = 0, SCAN_PRODUCT = 1, SCAN_COUNT = 2;   // SCAN_COUNT: integer addition, for the zero counts
+constexpr uint32_t SCAN_GROUP = 8, SCAN_THREADS = 256, SCAN_TILE = SCAN_GROUP * SCAN_THREADS, SCAN_WAVE = 64;
+constexpr uint32_t SCAN_INLINE_COLUMNS = 64;    // columns of one launch sequence: their seeds ride in the kernel arguments
+constexpr uint32_t SCAN_MAX_LOG_N = 27;
+constexpr uint32_t BB_RINV = cx_powmod(BB_R1, BB_P - 2);   // R^-1 mod p
+static_assert(cx_mulmod(BB_RINV, BB_R1) == 1u, "R^-1");
+template <int OP> TOYNI_HD uint32_t scan_identity() { return OP == (int)SCAN_PRODUCT ? BB_R1 : 0u; }
+template <int OP> TOYNI_HD uint32_t scan_combine(uint32_t a, uint32_t b) {
+    return OP == (int)SCAN_SUM ? bb_add(a, b) : OP == (int)SCAN_PRODUCT ? mont_mul(a, b) : a + b;
+}
+template <int OP> TOYNI_HD uint32_t scan_to_plain(uint32_t v) { return OP == (int)SCAN_PRODUCT ? from_mont(v) : v; }
+struct ScanArgs {
+    const uint32_t* num;     // column b at num + b * num_stride; null: every numerator is 1
+    const uint32_t* den;     // null: every denominator is 1
+    uint32_t* out;
+    uint64_t num_stride, den_stride, out_stride;
+    uint64_t n;
+    uint32_t* tiles;         // column b: ntiles aggregates (step 2 turns them into prefixes in place), then ntiles zero counts
+    uint32_t* totals;        // [column][2], may be null
+    uint32_t ntiles;
+    uint32_t single;         // n <= one tile: step 3 alone, seeded by init, writes the totals
+};
+struct ScanInit { uint32_t v[SCAN_INLINE_COLUMNS]; };   // init[b]: plain for sums, Montgomery form for products
+TOYNI_HD uint32_t* scan_tile_aggregates(const ScanArgs& a, uint32_t col) { return a.tiles + (uint64_t)col * 2u * a.ntiles; }
+TOYNI_HD uint32_t* scan_tile_zeros(const ScanArgs& a, uint32_t col) { return scan_tile_aggregates(a, col) + a.ntiles; }
+// the G words of a column from i0 on (i0 a multiple of G, G a multiple of 4): 16-byte loads where the column's first word is 16-byte
+// aligned and the group lies inside the column, guarded word loads otherwise; `fill` past the end
+template <int G>
+TOYNI_HD void scan_group_load(const uint32_t* col, uint64_t i0, uint64_t n, uint32_t fill, uint32_t (&v)[G]) {
+    static_assert(G % 4 == 0, "a group is whole quads");
+    if (!((uintptr_t)col & 15) && i0 + G <= n) {
+#pragma unroll
+        for (int q = 0; q < G / 4; ++q) {
+            const DeepQuad w = *reinterpret_cast<const DeepQuad*>(col + i0 + 4 * q);
+            v[4 * q] = w[0]; v[4 * q + 1] = w[1]; v[4 * q + 2] = w[2]; v[4 * q + 3] = w[3];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < G; ++j) v[j] = i0 + (uint64_t)j < n ? col[i0 + j] : fill;
+    }
+}
+template <int G>
+TOYNI_HD void scan_group_store(uint32_t* col, uint64_t i0, uint64_t n, const uint32_t (&v)[G]) {
+    if (!((uintptr_t)col & 15) && i0 + G <= n) {
+#pragma unroll
+        for (int q = 0; q < G / 4; ++q) *reinterpret_cast<DeepQuad*>(col + i0 + 4 * q) = DeepQuad{v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < G; ++j)
+            if (i0 + (uint64_t)j < n) col[i0 + j] = v[j];
+    }
+}
+// x_j = den_j^-1 * R * c (0 where den_j = 0) for the G plain residues den[]: ONE Fermat inversion (Montgomery's trick, zeros kept out
+// of the chain with the marker of deep_point_inverses).  A plain residue d is read as the Montgomery form of d / R, so no operand is
+// converted: the chain yields (d / R)^-1 R = d^-1 R^2, and the one factor c that the inverted product is multiplied by decides the form
+// of all G results -- c = R: d^-1 R^2 (times a plain numerator: a Montgomery form), c = 1: d^-1 R, c = R^-1: d^-1.  Returns the zeros met.
+template <int G>
+TOYNI_HD uint32_t scan_group_inverses(uint32_t (&d)[G], uint32_t c, uint32_t (&x)[G]) {
+    uint32_t pre[G];
+    uint32_t acc = BB_R1, zeros = 0;
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+        if (d[j] == 0u) d[j] = BB_R1 | 0x80000000u;   // marker (never a canonical value)
+        pre[j] = acc;
+        acc = mont_mul(acc, (d[j] & 0x80000000u) ? BB_R1 : d[j]);
+    }
+    uint32_t inv = mont_mul(mont_inv_chain(acc), c);
+#pragma unroll
+    for (int j = G - 1; j >= 0; --j) {
+        const bool zero = (d[j] & 0x80000000u) != 0u;
+        x[j] = zero ? 0u : mont_mul(inv, pre[j]);
+        if (!zero) inv = mont_mul(inv, d[j]);
+        zeros += zero ? 1u : 0u;
+    }
+    return zeros;
+}
+// the G terms from i0 on in the form the op scans (plain for a sum, Montgomery for a product); the identity past n.  numc / denc: the
+// column's operands (one of them may be null).  Returns the zero denominators met below n.
+template <int OP, int G>
+TOYNI_HD uint32_t scan_group_terms(const uint32_t* numc, const uint32_t* denc, uint64_t i0, uint64_t n, uint32_t (&t)[G]) {
+    constexpr bool PROD = OP == (int)SCAN_PRODUCT;
+    uint32_t zeros = 0;
+    if (denc) {
+        uint32_t d[G], x[G];
+        scan_group_load<G>(denc, i0, n, 1u, d);   // past n: 1, which is no zero
+        zeros = scan_group_inverses<G>(d, numc ? (PROD ? BB_R1 : 1u) : (PROD ? 1u : BB_RINV), x);
+        if (numc) {
+            uint32_t u[G];
+            scan_group_load<G>(numc, i0, n, 0u, u);
+#pragma unroll
+            for (int j = 0; j < G; ++j) t[j] = mont_mul(u[j], x[j]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < G; ++j) t[j] = x[j];
+        }
+    } else {
+        scan_group_load<G>(numc, i0, n, 0u, t);
+        if (PROD) {
+#pragma unroll
+            for (int j = 0; j < G; ++j) t[j] = to_mont(t[j]);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < G; ++j)
+        if (i0 + (uint64_t)j >= n) t[j] = scan_identity<OP>();
+    return zeros;
+}
+// thread-serial part: ex[j] = t[0] o ... o t[j-1]; returns the group's total
+template <int OP, int G>
+TOYNI_HD uint32_t scan_thread_serial(const uint32_t (&t)[G], uint32_t (&ex)[G]) {
+    uint32_t acc = scan_identity<OP>();
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+        ex[j] = acc;
+        acc = scan_combine<OP>(acc, t[j]);
+    }
+    return acc;
+}
+// THE cross-lane step of the scans: the value of the lane `delta` below (a lane below `delta` gets its own value back).  On the device
+// one ds_bpermute_b32 (__shfl_up); on the CPU the wave is an array of 64 values that tests/emu steps lane by lane.
+#if defined(__HIPCC__)
+TOYNI_DEV uint32_t scan_lane_up(uint32_t v, uint32_t delta) { return (uint32_t)__shfl_up((int)v, delta, (int)SCAN_WAVE); }
+#endif
+inline uint32_t scan_lane_up(const uint32_t (&wave)[SCAN_WAVE], uint32_t lane, uint32_t delta) { return wave[lane >= delta ? lane - delta : lane]; }
+// one of the log2(64) steps of the inclusive scan across a wave's lanes (Hillis-Steele: delta = 1, 2, 4 ... 32)
+template <int OP> TOYNI_HD uint32_t scan_wave_step(uint32_t v, uint32_t below, uint32_t lane, uint32_t delta) {
+    return lane >= delta ? scan_combine<OP>(below, v) : v;
+}
+// from the waves' totals (LDS): what the waves below `wave` add up to; `total` = all of them
+template <int OP, int NW>
+TOYNI_HD uint32_t scan_waves_below(const uint32_t* wave_tot, uint32_t wave, uint32_t& total) {
+    uint32_t pre = scan_identity<OP>();
+    total = scan_identity<OP>();
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        if ((uint32_t)w == wave) pre = total;
+        total = scan_combine<OP>(total, wave_tot[w]);
+    }
+    return pre;
+}
+// what step 3 stores: base o ex[j], as plain residues
+template <int OP, int G>
+TOYNI_HD void scan_group_finish(uint32_t base, const uint32_t (&ex)[G], uint32_t (&o)[G]) {
+#pragma unroll
+    for (int j = 0; j < G; ++j) o[j] = scan_to_plain<OP>(scan_combine<OP>(base, ex[j]));
+}
+
 // ---- polynomial evaluation at up to POLY_MAX_POINTS points ----
 constexpr int POLY_MAX_POINTS = 4;
 constexpr uint32_t POLY_PER_THREAD = 16, POLY_THREADS = 256, POLY_CHUNK = POLY_PER_THREAD * POLY_THREADS;

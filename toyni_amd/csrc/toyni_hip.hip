@@ -827,6 +827,107 @@ __global__ void __launch_bounds__(256) air_quotient_kernel(const AirArgs a, cons
 struct AirInlineWeights { uint32_t w[AIR_INLINE_WEIGHTS]; };
 __global__ void __launch_bounds__(256) air_quotient_inline_kernel(const AirArgs a, const AirInlineWeights in) { air_quotient_body(a, in.w); }
 
+// Accumulator columns (prover_kernels.hpp, include/toyni_hip.h 3g).  Every workgroup is SCAN_THREADS threads, every thread owns
+// SCAN_GROUP consecutive elements.  The workgroup-wide scan: thread-serial over the group (the caller), log2(64) cross-lane steps
+// inside each wave, the waves' totals through LDS.  Every thread of the workgroup reaches both barriers.
+template <int OP>
+__device__ __forceinline__ uint32_t scan_wave_inclusive(uint32_t v, uint32_t lane) {
+#pragma unroll
+    for (uint32_t delta = 1; delta < SCAN_WAVE; delta <<= 1) v = scan_wave_step<OP>(v, scan_lane_up(v, delta), lane, delta);
+    return v;
+}
+// what the threads below this one add up to, and in `total` the whole workgroup's; wave_tot: SCAN_THREADS / 64 words of LDS
+template <int OP>
+__device__ __forceinline__ uint32_t scan_block_exclusive(uint32_t v, uint32_t* wave_tot, uint32_t& total) {
+    constexpr int NW = SCAN_THREADS / SCAN_WAVE;
+    const uint32_t lane = threadIdx.x & (SCAN_WAVE - 1), wave = threadIdx.x / SCAN_WAVE;
+    const uint32_t inc = scan_wave_inclusive<OP>(v, lane);
+    if (lane == SCAN_WAVE - 1) wave_tot[wave] = inc;
+    __syncthreads();
+    const uint32_t up = scan_lane_up(inc, 1);
+    const uint32_t pre = scan_waves_below<OP, NW>(wave_tot, wave, total);
+    __syncthreads();   // wave_tot may be written again
+    return lane ? scan_combine<OP>(pre, up) : pre;
+}
+// step 1, grid (tile, column): one aggregate and one zero count per tile
+template <int OP>
+__global__ void __launch_bounds__(SCAN_THREADS) column_scan_aggregate_kernel(const ScanArgs a) {
+    __shared__ uint32_t wave_tot[SCAN_THREADS / SCAN_WAVE];
+    const uint32_t col = blockIdx.y, tile = blockIdx.x;
+    const uint64_t i0 = (uint64_t)tile * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_GROUP;
+    uint32_t t[SCAN_GROUP], ex[SCAN_GROUP], total, ztotal;
+    const uint32_t zeros = scan_group_terms<OP, SCAN_GROUP>(a.num ? a.num + col * a.num_stride : nullptr, a.den ? a.den + col * a.den_stride : nullptr,
+                                                            i0, a.n, t);
+    (void)scan_block_exclusive<OP>(scan_thread_serial<OP, SCAN_GROUP>(t, ex), wave_tot, total);
+    (void)scan_block_exclusive<SCAN_COUNT>(zeros, wave_tot, ztotal);
+    if (threadIdx.x == 0) {
+        scan_tile_aggregates(a, col)[tile] = total;
+        scan_tile_zeros(a, col)[tile] = ztotal;
+    }
+}
+// step 2, one workgroup per column: the exclusive scan of the column's aggregates, seeded with init, in rounds of SCAN_TILE; the totals
+template <int OP>
+__global__ void __launch_bounds__(SCAN_THREADS) column_scan_prefix_kernel(const ScanArgs a, const ScanInit in) {
+    __shared__ uint32_t wave_tot[SCAN_THREADS / SCAN_WAVE];
+    const uint32_t col = blockIdx.x;
+    uint32_t* agg = scan_tile_aggregates(a, col);
+    uint32_t carry = in.v[col];
+    for (uint32_t base = 0; base < a.ntiles; base += SCAN_TILE) {
+        const uint64_t i0 = (uint64_t)base + threadIdx.x * SCAN_GROUP;
+        uint32_t t[SCAN_GROUP], ex[SCAN_GROUP], total;
+        scan_group_load<SCAN_GROUP>(agg, i0, a.ntiles, scan_identity<OP>(), t);
+        const uint32_t pre = scan_block_exclusive<OP>(scan_thread_serial<OP, SCAN_GROUP>(t, ex), wave_tot, total);
+        const uint32_t mine = scan_combine<OP>(carry, pre);
+#pragma unroll
+        for (int j = 0; j < (int)SCAN_GROUP; ++j) t[j] = scan_combine<OP>(mine, ex[j]);
+        scan_group_store<SCAN_GROUP>(agg, i0, a.ntiles, t);
+        carry = scan_combine<OP>(carry, total);
+    }
+    const uint32_t* zc = scan_tile_zeros(a, col);
+    uint32_t zeros = 0, ztotal;
+    for (uint32_t k = threadIdx.x; k < a.ntiles; k += SCAN_THREADS) zeros += zc[k];
+    (void)scan_block_exclusive<SCAN_COUNT>(zeros, wave_tot, ztotal);
+    if (threadIdx.x == 0 && a.totals) {
+        a.totals[2 * col] = scan_to_plain<OP>(carry);
+        a.totals[2 * col + 1] = ztotal;
+    }
+}
+// step 3, grid (tile, column): the terms again, the scan inside the tile on top of the tile's prefix.  With a.single the grid is the
+// columns alone (n <= one tile): the prefix is init and the totals are written here.
+template <int OP>
+__global__ void __launch_bounds__(SCAN_THREADS) column_scan_apply_kernel(const ScanArgs a, const ScanInit in) {
+    __shared__ uint32_t wave_tot[SCAN_THREADS / SCAN_WAVE];
+    const uint32_t col = blockIdx.y, tile = blockIdx.x;
+    const uint64_t i0 = (uint64_t)tile * SCAN_TILE + (uint64_t)threadIdx.x * SCAN_GROUP;
+    uint32_t t[SCAN_GROUP], ex[SCAN_GROUP], total;
+    const uint32_t zeros = scan_group_terms<OP, SCAN_GROUP>(a.num ? a.num + col * a.num_stride : nullptr, a.den ? a.den + col * a.den_stride : nullptr,
+                                                            i0, a.n, t);
+    const uint32_t pre = scan_block_exclusive<OP>(scan_thread_serial<OP, SCAN_GROUP>(t, ex), wave_tot, total);
+    const uint32_t seed = a.single ? in.v[col] : TOYNI_UNIFORM(scan_tile_aggregates(a, col)[tile]);
+    scan_group_finish<OP, SCAN_GROUP>(scan_combine<OP>(seed, pre), ex, t);
+    scan_group_store<SCAN_GROUP>(a.out + col * a.out_stride, i0, a.n, t);
+    if (a.single) {
+        uint32_t ztotal;
+        (void)scan_block_exclusive<SCAN_COUNT>(zeros, wave_tot, ztotal);
+        if (threadIdx.x == 0 && a.totals) {
+            a.totals[2 * col] = scan_to_plain<OP>(scan_combine<OP>(seed, total));
+            a.totals[2 * col + 1] = ztotal;
+        }
+    }
+}
+// out[i] = in[i]^-1 (0 for 0): the term-forming group body alone.  zero_count (may be null) was cleared ahead of the launch.
+__global__ void __launch_bounds__(SCAN_THREADS) batch_inverse_kernel(const uint32_t* in, uint32_t* out, uint64_t count, uint32_t* zero_count) {
+    const uint64_t i0 = ((uint64_t)blockIdx.x * SCAN_THREADS + threadIdx.x) * SCAN_GROUP;
+    uint32_t t[SCAN_GROUP];
+    const uint32_t zeros = scan_group_terms<SCAN_SUM, SCAN_GROUP>(nullptr, in, i0, count, t);
+    scan_group_store<SCAN_GROUP>(out, i0, count, t);
+    if (zero_count) {
+        const uint32_t lane = threadIdx.x & (SCAN_WAVE - 1);
+        const uint32_t wave_zeros = scan_wave_inclusive<SCAN_COUNT>(zeros, lane);
+        if (lane == SCAN_WAVE - 1 && wave_zeros) atomicAdd(zero_count, wave_zeros);
+    }
+}
+
 // Merkle openings: one thread per (opening, level) copies the sibling digest; one thread per opening adds salt, value, flags
 struct OpenGroup {
     const Digest* levels;
@@ -1763,6 +1864,18 @@ int host_stage_reserve(HostStage* st, int slot, size_t bytes) {
     HIPCHK(hipMalloc(&st->buf[slot], bytes));
     st->cap[slot] = bytes;
     return 0;
+}
+
+// the launch sequence of toyni_column_scan_device for up to SCAN_INLINE_COLUMNS columns
+template <int OP>
+void column_scan_launch(const ScanArgs& a, const ScanInit& in, unsigned cols, hipStream_t s) {
+    if (a.single) {
+        hipLaunchKernelGGL(column_scan_apply_kernel<OP>, dim3(1, cols), dim3(SCAN_THREADS), 0, s, a, in);
+        return;
+    }
+    hipLaunchKernelGGL(column_scan_aggregate_kernel<OP>, dim3(a.ntiles, cols), dim3(SCAN_THREADS), 0, s, a);
+    hipLaunchKernelGGL(column_scan_prefix_kernel<OP>, dim3(cols), dim3(SCAN_THREADS), 0, s, a, in);
+    hipLaunchKernelGGL(column_scan_apply_kernel<OP>, dim3(a.ntiles, cols), dim3(SCAN_THREADS), 0, s, a, in);
 }
 
 bool is_pow2(size_t v) { return v && !(v & (v - 1)); }
@@ -3045,6 +3158,63 @@ int toyni_deep_combine_device(toyni_ntt_ctx* c, const uint32_t* d_values, size_t
     std::memcpy(h, table.data(), nterms * sizeof(DeepTerm));
     HIPCHK(hipMemcpyAsync(sc.d_lde32, h, nterms * sizeof(DeepTerm), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(deep_combine_kernel, grid, dim3(256), 0, s, a, reinterpret_cast<const DeepTerm*>(sc.d_lde32));
+    return (int)hipGetLastError();
+}
+
+// ---- section 3g: accumulator columns ----
+size_t toyni_column_scan_tile(void) { return SCAN_TILE; }
+
+int toyni_batch_inverse_device(const uint32_t* d_in, uint32_t* d_out, size_t count, uint32_t* d_zero_count, void* stream) {
+    if (!d_in || !d_out) return TOYNI_E_NULL;
+    if (count > ((size_t)1 << 32) || (((uintptr_t)d_in | (uintptr_t)d_out | (uintptr_t)d_zero_count) & 3)) return TOYNI_E_RANGE;
+    hipStream_t s = (hipStream_t)stream;
+    if (d_zero_count) HIPCHK(hipMemsetAsync(d_zero_count, 0, sizeof(uint32_t), s));
+    if (count == 0) return TOYNI_OK;
+    hipLaunchKernelGGL(batch_inverse_kernel, dim3((unsigned)((count + SCAN_TILE - 1) / SCAN_TILE)), dim3(SCAN_THREADS), 0, s, d_in, d_out,
+                       (uint64_t)count, d_zero_count);
+    return (int)hipGetLastError();
+}
+
+int toyni_column_scan_device(toyni_ntt_ctx* c, const uint32_t* d_num, size_t num_stride, const uint32_t* d_den, size_t den_stride, uint32_t* d_out,
+                             size_t out_stride, size_t n, size_t batch, int op, const uint32_t* init, uint32_t* d_totals, void* stream) {
+    // every refusal is decided on the arguments alone: the context is not touched before they have passed
+    if (!c || !d_out || !init || (!d_num && !d_den)) return TOYNI_E_NULL;
+    if ((op != TOYNI_SCAN_SUM && op != TOYNI_SCAN_PRODUCT) || n > ((size_t)1 << SCAN_MAX_LOG_N) || batch >= ((size_t)1 << 16) ||
+        (((uintptr_t)d_num | (uintptr_t)d_den | (uintptr_t)d_out | (uintptr_t)d_totals) & 3))
+        return TOYNI_E_RANGE;
+    if (batch > 1 && ((d_num && num_stride < n) || (d_den && den_stride < n) || out_stride < n)) return TOYNI_E_RANGE;
+    for (size_t b = 0; b < batch; ++b)
+        if (init[b] >= BB_P) return TOYNI_E_RANGE;
+    if (batch == 0 || n == 0) return TOYNI_OK;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    ScanArgs a{};
+    a.num_stride = num_stride;
+    a.den_stride = den_stride;
+    a.out_stride = out_stride;
+    a.n = n;
+    a.ntiles = (uint32_t)((n + SCAN_TILE - 1) / SCAN_TILE);
+    a.single = a.ntiles == 1 ? 1u : 0u;
+    if (!a.single) {   // the aggregates and zero counts of one launch sequence's columns; a warm context finds the buffer in place
+        toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+        int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words, 2 * (size_t)a.ntiles * std::min<size_t>(batch, SCAN_INLINE_COLUMNS), sizeof(uint32_t));
+        if (rc) return rc;
+        a.tiles = sc.d_lde32;
+    }
+    // the seeds ride in the kernel arguments, SCAN_INLINE_COLUMNS columns to a launch sequence (the stream orders the sequences, so
+    // they share the buffer)
+    for (size_t b0 = 0; b0 < batch; b0 += SCAN_INLINE_COLUMNS) {
+        const unsigned cols = (unsigned)std::min<size_t>(batch - b0, SCAN_INLINE_COLUMNS);
+        ScanInit in{};
+        for (unsigned b = 0; b < cols; ++b) in.v[b] = op == TOYNI_SCAN_PRODUCT ? to_mont_host(init[b0 + b]) : init[b0 + b];
+        a.num = d_num ? d_num + b0 * num_stride : nullptr;
+        a.den = d_den ? d_den + b0 * den_stride : nullptr;
+        a.out = d_out + b0 * out_stride;
+        a.totals = d_totals ? d_totals + 2 * b0 : nullptr;
+        if (op == TOYNI_SCAN_PRODUCT) column_scan_launch<SCAN_PRODUCT>(a, in, cols, s);
+        else column_scan_launch<SCAN_SUM>(a, in, cols, s);
+    }
     return (int)hipGetLastError();
 }
 

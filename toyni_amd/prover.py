@@ -250,6 +250,35 @@ class AirBuilder:
         return insns
 
 
+# ---- accumulator columns (include/toyni_hip.h 3g) ----
+SCAN_SUM, SCAN_PRODUCT = 0, 1
+
+
+def column_scan_tile() -> int:
+    """Elements one workgroup owns: a column of at most this many takes a single launch."""
+    return lib.toyni_column_scan_tile()
+
+
+def batch_inverse_device(d_in: int, d_out: int, count: int, d_zero_count: int = 0, stream=None) -> None:
+    """d_out[i] = d_in[i]^-1, 0 for 0; d_zero_count (one device word, optional) receives the number of zeros.  d_out may be d_in."""
+    check(lib.toyni_batch_inverse_device(d_in, d_out, count, d_zero_count or None, stream or None), "GPU batch inversion failed")
+
+
+def column_scan_device(ctx, num: int, den: int, out: int, n: int, batch: int = 1, op: int = SCAN_SUM, init=None, totals: int = 0, strides=None,
+                       stream=None) -> None:
+    """out[0] = init[b], out[i] = out[i-1] (+ or *) num[i-1] / den[i-1] for each of `batch` columns (include/toyni_hip.h 3g): the
+    accumulator column of a LogUp sum or of a permutation product.  num or den may be 0 (absent: ones); a zero denominator makes the
+    term 0.  init: one residue per column (default: the op's identity).  totals: 2 * batch device words, optional: the wrap-around
+    value and the zero denominators of each column.  strides: (num, den, out) words between columns, default n each."""
+    if init is None:
+        init = [1 if op == SCAN_PRODUCT else 0] * batch
+    i = np.ascontiguousarray(init, dtype=np.uint32)
+    assert i.size == batch
+    ns, ds, os_ = strides if strides is not None else (n, n, n)
+    check(lib.toyni_column_scan_device(ctx.handle, num or None, ns, den or None, ds, out, os_, n, batch, op, i.ctypes.data, totals or None,
+                                       stream or None), "GPU column scan failed")
+
+
 def merkle_open_record_bytes(n: int) -> int:
     return lib.toyni_merkle_open_record_bytes(n)
 
