@@ -45,6 +45,7 @@ static int failures = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { ++failures; std::printf("FAIL %s:%d: ", __FILE__, __LINE__); std::printf(__VA_ARGS__); std::printf("\n"); } } while (0)
 
 // one tile of a pass, phase by phase: every thread runs phase k before any thread runs phase k + 1 (the pass' barriers)
+// (the schedule restated here is checked against the kernels' own in tests/sim)
 static unsigned long long tiles_by_steps[4] = {0, 0, 0, 0};
 static LaunchKnobs knobs = launch_knobs();   // the process's dispatch knobs; "pN" / "wN" move two of them
 static bool latency_plan = false;   // "Q1": n = 2^21 / 2^22 through their two-pass plans (2048-point three-step shapes)

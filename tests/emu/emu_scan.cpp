@@ -1,7 +1,8 @@
 // Steps the bodies of the accumulator-column kernels (scan_group_terms, scan_thread_serial, scan_wave_step, scan_waves_below,
 // scan_group_finish ...: toyni_amd/csrc/prover_kernels.hpp, include/toyni_hip.h 3g) on the CPU: workgroup by workgroup, wave by
 // wave, and inside a wave's cross-lane steps lane by lane on an array of 64 values (the CPU form of scan_lane_up).  The glue between
-// the bodies -- which value goes through LDS, where the barriers stand -- restates column_scan_*_kernel of toyni_hip.hip on a REDUCED
+// the bodies -- which value goes through LDS, where the barriers stand -- restates column_scan_*_kernel of toyni_hip.hip (the schedule
+// restated here is checked against the kernels' own in tests/sim) on a REDUCED
 // tile (groups of 4, workgroups of 128 threads = two waves: 512 elements), so that every edge is met at a small size.  Prints
 //     SCAN <op> <n> <batch> <has_num> <has_den> <in place: 0 no, 1 on num, 2 on den> <word offset> <strides: num den out>
 //     INIT <batch values>

@@ -26,7 +26,7 @@
 // a value that is the same in every lane: on the device force it into an SGPR
 #if defined(__HIP_DEVICE_COMPILE__)
 #define TOYNI_UNIFORM(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
-#else
+#elif !defined(TOYNI_UNIFORM)   // (the host forms of the synchronisation macros can be defined first: tests/sim hooks them)
 #define TOYNI_UNIFORM(x) (x)
 #endif
 
@@ -46,13 +46,23 @@
 // LDS operations (lgkmcnt), i.e. "my writes have landed"; TOYNI_BARRIER is the bare rendezvous ("everyone has read").
 #define TOYNI_BARRIER() asm volatile("s_barrier" ::: "memory")
 #define TOYNI_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+// No barrier at all, where a wave reads back only what the same wave wrote: the LDS operations of a wave execute in program order,
+// so all that is needed is that the COMPILER keeps them on their side.
+#define TOYNI_WAVE_ORDER() asm volatile("" ::: "memory")
 #else
 #define TOYNI_SCHED_FENCE() ((void)0)
 #define TOYNI_PIN(v) ((void)0)
 #define TOYNI_WAIT_VMEM0() ((void)0)
 #define TOYNI_WAIT_VMEM_ALLOW(N) ((void)0)
+#ifndef TOYNI_BARRIER
 #define TOYNI_BARRIER() ((void)0)
+#endif
+#ifndef TOYNI_LDS_BARRIER
 #define TOYNI_LDS_BARRIER() ((void)0)
+#endif
+#ifndef TOYNI_WAVE_ORDER
+#define TOYNI_WAVE_ORDER() ((void)0)
+#endif
 #endif
 
 namespace toyni {

@@ -500,7 +500,7 @@ TOYNI_HD uint32_t scan_thread_serial(const uint32_t (&t)[G], uint32_t (&ex)[G]) 
 }
 // THE cross-lane step of the scans: the value of the lane `delta` below (a lane below `delta` gets its own value back).  On the device
 // one ds_bpermute_b32 (__shfl_up); on the CPU the wave is an array of 64 values that tests/emu steps lane by lane.
-#if defined(__HIPCC__)
+#if defined(__HIPCC__) || defined(TOYNI_KERNEL_TEXT_ONLY)
 TOYNI_DEV uint32_t scan_lane_up(uint32_t v, uint32_t delta) { return (uint32_t)__shfl_up((int)v, delta, (int)SCAN_WAVE); }
 #endif
 inline uint32_t scan_lane_up(const uint32_t (&wave)[SCAN_WAVE], uint32_t lane, uint32_t delta) { return wave[lane >= delta ? lane - delta : lane]; }

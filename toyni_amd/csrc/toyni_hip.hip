@@ -1,6 +1,9 @@
 // libtoyni_hip.so -- gfx950 kernels + C ABI (include/toyni_hip.h).
 // Replaces cuda/ntt_kernel.cu of the reference; written for CDNA4 only (wave64, 160 KiB LDS, no MFMA:
 // the path is integer modular arithmetic).  Kernel bodies live in ntt_kernels.hpp.
+// TOYNI_KERNEL_TEXT_ONLY (tests/sim; never a product build): the kernel section alone -- no HIP runtime, no launch registry, no
+// context and no C ABI -- for a translation unit that supplies the handful of HIP names the kernels use and runs them on the CPU.
+#ifndef TOYNI_KERNEL_TEXT_ONLY
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
@@ -17,6 +20,7 @@
 #ifdef TOYNI_TOOLS
 #include "toyni_hip_tools.h"
 #endif
+#endif  // TOYNI_KERNEL_TEXT_ONLY
 #include "toyni_hip.h"  // include/toyni_hip.h: -I include here; next to this file in a crate's hip/ directory
 #include "ntt_plan.hpp"
 #include "merkle_kernels.hpp"
@@ -24,6 +28,7 @@
 
 using namespace toyni;
 
+#ifndef TOYNI_KERNEL_TEXT_ONLY
 // ------------------------------------------------------------------------------------------------
 // launch registry (toyni_launched_kernels, include/toyni_hip.h section 4)
 // ------------------------------------------------------------------------------------------------
@@ -65,6 +70,7 @@ inline bool note(const void* host_fn) {
         hipError_t _e = (expr);                        \
         if (_e != hipSuccess) return (int)_e;          \
     } while (0)
+#endif  // TOYNI_KERNEL_TEXT_ONLY
 
 // ------------------------------------------------------------------------------------------------
 // kernels
@@ -238,7 +244,7 @@ __global__ void __launch_bounds__(P::T, P::MIN_WAVES) ntt_pass3s_kernel(const Pa
             inraw = P::in_seed_issue(a, tn, tid);
         }
         TOYNI_SCHED_FENCE();
-        if constexpr (P::WAVE_LOCAL2) asm volatile("" ::: "memory");   // step 2 reads what this wave itself wrote: program order suffices
+        if constexpr (P::WAVE_LOCAL2) TOYNI_WAVE_ORDER();   // step 2 reads what this wave itself wrote: program order suffices
         else TOYNI_LDS_BARRIER();
         TOYNI_SCHED_FENCE();
         P::step2_regs(tid, lds, tw2);
@@ -304,7 +310,7 @@ __global__ void __launch_bounds__(Row2048::T, 4) ntt_row2048_kernel(const PassAr
     using R = Row2048;
     __shared__ uint32_t lds[R::LDS_WORDS + R::TW1_WORDS + R::TW3_WORDS + R::TW2_WORDS];
     const uint32_t tid = threadIdx.x, l = tid & 63u;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
+    const uint32_t wave = TOYNI_UNIFORM(tid >> 6);
     uint32_t* lds_tw1 = lds + R::LDS_WORDS;
     uint32_t* lds_tw3 = lds_tw1 + R::TW1_WORDS;
     uint32_t* lds_tw2 = lds_tw3 + R::TW3_WORDS;
@@ -329,12 +335,12 @@ __global__ void __launch_bounds__(Row2048::T, 4) ntt_row2048_kernel(const PassAr
         const bool more = next < a.rows_total;  // wave-uniform
         if (more) R::template load_row<NT>(a, next, l, x);   // prefetch
         TOYNI_SCHED_FENCE();
-        asm volatile("" ::: "memory");     // steps 2 and 3 read what this wave itself wrote: program order suffices (LDS operations of a wave execute in order)
+        TOYNI_WAVE_ORDER();                // steps 2 and 3 read what this wave itself wrote: program order suffices (LDS operations of a wave execute in order)
         R::step2(l, row_lds, lds_tw2);
-        asm volatile("" ::: "memory");
+        TOYNI_WAVE_ORDER();
         R::template step3<NT>(a, c, row, l, row_lds);
         if (!more) break;
-        asm volatile("" ::: "memory");
+        TOYNI_WAVE_ORDER();
         row = next;
     }
 }
@@ -347,7 +353,7 @@ __global__ void __launch_bounds__(Row4096::T, 4) ntt_row4096_kernel(const PassAr
     using R = Row4096;
     __shared__ uint32_t lds[R::LDS_WORDS + R::TW1_WORDS + R::TW2_WORDS];
     const uint32_t tid = threadIdx.x, tau = tid & 127u;
-    const uint32_t rho = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 7));
+    const uint32_t rho = TOYNI_UNIFORM(tid >> 7);
     uint32_t* lds_tw1 = lds + R::LDS_WORDS;
     uint32_t* lds_tw2 = lds_tw1 + R::TW1_WORDS;
     uint32_t* row_lds = lds + rho * R::ROW_WORDS;
@@ -769,7 +775,11 @@ __global__ void __launch_bounds__(256) deep_combine_inline_kernel(const DeepComb
 // grid-stride loop: every read of the program and of the weights precedes the thread's only global stores, so both are fetched
 // by scalar loads.  Dynamic LDS: [nregs][threads] slots of 16 bytes (the register file, sized from the program), then 1 / Z_H of
 // the B residue classes when they fit (a.zh_lds).
+#ifndef TOYNI_KERNEL_TEXT_ONLY
 extern __shared__ __align__(16) uint32_t air_lds[];
+#else
+extern __align__(16) uint32_t air_lds[];   // (`extern static` is not C++: the including translation unit defines the array)
+#endif
 __device__ __forceinline__ void air_quotient_body(const AirArgs& a, const uint32_t* weights) {
     constexpr int K = 4;
     const uint32_t B = 1u << a.log_blowup;
@@ -1273,7 +1283,7 @@ __device__ inline Digest merkle_node_coop(const Digest& l, const Digest& r, uint
 __global__ void __launch_bounds__(128) merkle_level_coop_kernel(const Digest* __restrict__ cur, Digest* __restrict__ next, size_t m, size_t up) {
     __shared__ uint32_t sched[COOP_SCHED_WORDS];
     const uint32_t lane = threadIdx.x & 63u;
-    const bool helper = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) != 0;
+    const bool helper = TOYNI_UNIFORM(threadIdx.x >> 6) != 0;
     const size_t i0 = (size_t)blockIdx.x * 64u + lane;
     const size_t i = i0 < up ? i0 : up - 1;
     const Digest l = cur[2 * i];
@@ -1306,7 +1316,7 @@ __global__ void __launch_bounds__(MERKLE_TAIL_T) merkle_tail_kernel(const Digest
     for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) lvl[i] = cur[i];
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t wave = TOYNI_UNIFORM(threadIdx.x >> 6);
     const uint32_t pair = wave >> 1;
     const bool helper = (wave & 1u) != 0u;
     while (m > 1) {
@@ -1331,6 +1341,7 @@ __global__ void __launch_bounds__(MERKLE_TAIL_T) merkle_tail_kernel(const Digest
     if (notify && threadIdx.x == 0) merkle_notify(lvl[0], notify, seq);
 }
 
+#ifndef TOYNI_KERNEL_TEXT_ONLY
 // ------------------------------------------------------------------------------------------------
 // context
 // ------------------------------------------------------------------------------------------------
@@ -3607,3 +3618,4 @@ const char* cuda_get_error_string(int error) { return toyni_error_string(error);
 
 // multi-GPU forms for a single-process host: cached per-device contexts, batch sharding, one transform over G devices
 #include "multi_gpu.hpp"
+#endif  // TOYNI_KERNEL_TEXT_ONLY
