@@ -20,7 +20,8 @@
  *            row openings' d_values / d_indices (checked: TOYNI_E_RANGE below 4 bytes; a 16-byte aligned row-major matrix whose width
  *            is a multiple of 4 takes 16-byte loads, others word loads)
  *   8 bytes  u64 pointers (toyni_ntt_device_u64, the narrow / widen pair) and the openings' d_out (row openings included)
- *   16 bytes the Ext folds' d_evals / d_out (one 16-byte access per Ext element; d_xs needs 4), the slab relayout's and the fused
+ *   16 bytes the Ext folds' d_evals / d_out (one 16-byte access per Ext element; d_xs needs 4), the Ext DEEP combination's d_out (3h),
+ *            the slab relayout's and the fused
  *            slab rows' d_in / d_out, every Merkle d_levels / d_salts, the ChaCha20 fill's d_out
  *
  * Threading and streams: a context serialises the ENQUEUEING of its calls with an internal mutex, and keeps its
@@ -459,6 +460,48 @@ int toyni_batch_inverse_device(const uint32_t* d_in, uint32_t* d_out, size_t cou
 int toyni_column_scan_device(toyni_ntt_ctx* ctx, const uint32_t* d_num, size_t num_stride, const uint32_t* d_den, size_t den_stride,
                              uint32_t* d_out, size_t out_stride, size_t n, size_t batch, int op, const uint32_t* init,
                              uint32_t* d_totals, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 3h. The two steps of 3e under Ext-valued challenges: the protocol shape a STARK over this field uses (src/ext.rs:1-8 -- the trace and
+ *     the evaluation domain stay in the base field, the random challenges and what derives from them live in the quartic extension;
+ *     src/transcript.rs:41-55 squeeze_ext_challenge / absorb_ext).  This is the one step that takes base-field columns to an Ext-valued
+ *     codeword; with it the sequence
+ *         batched inverse transform -> toyni_lde_device(batch = w) -> toyni_merkle_commit_rows_device
+ *         -> toyni_poly_eval_ext_batch_device -> toyni_deep_combine_ext_device
+ *         -> toyni_fri_fold_ext_device / toyni_merkle_commit_rows_device(TOYNI_ROWS_ROW_MAJOR, width = 4) per round
+ *     stays on the device.  The quotient under Ext weights needs nothing new: toyni_air_quotient_device is linear in its weights, so
+ *     four calls with the coordinates of the weights write the quotient's four base columns, which join the DEEP combination as a
+ *     second matrix (accumulate).  An Ext-valued polynomial held as four base columns q_0..q_3 (that quotient, later an Ext
+ *     accumulator) needs no entry point of its own either: evaluate the four columns here and combine on the host,
+ *     q(z) = sum_j X^j q_j(z).
+ *     Ext = F_p[X]/(X^4 - 11), four consecutive words c0..c3 (section 3).  Every convention is that of 3e: asynchronous on `stream`,
+ *     packed-u32 canonical residues in and out, `points`, `z` and `terms` are host arrays that the caller may reuse as soon as the call
+ *     returns, the context lends its device, its lock and its per-stream intermediate buffer.
+ *     Refused before anything is enqueued, the outputs untouched -- TOYNI_E_NULL for a null context or pointer; TOYNI_E_RANGE for the
+ *     list of 3e, with "a point, z, alpha or value >= p" read per coordinate, and for a d_out of toyni_deep_combine_ext_device that is
+ *     not 16-byte aligned (the Ext folds that consume it demand that; every other device pointer: 4 bytes).
+ * ---------------------------------------------------------------------------------------------- */
+/* d_out[(b * npoints + p) * 4 + k] = coordinate k of sum_i d_coeffs[b * stride + i] * points[p]^i,  i < ncoeffs,  b < batch,
+ * 1 <= npoints <= 4; points: npoints x 4 words.  Base coefficients, Ext points and values; with a point embedded from the base field
+ * coordinate 0 is toyni_poly_eval_batch_device's word and the others are 0.  Two launches for the whole batch.  ncoeffs == 0 writes
+ * batch x npoints x 4 zeros; batch == 0 succeeds and writes nothing. */
+int toyni_poly_eval_ext_batch_device(toyni_ntt_ctx* ctx, const uint32_t* d_coeffs, size_t ncoeffs, size_t stride, size_t batch,
+                                     const uint32_t* points, unsigned npoints, uint32_t* d_out, void* stream);
+typedef struct { uint32_t column, rotation; uint32_t alpha[4]; uint32_t value[4]; } toyni_deep_ext_term;
+/* With N, B, x_i and M(c, i) as in toyni_deep_combine_device (a base-field, column-major matrix):
+ *   d_i = ( sum_t alpha_t * (M(column_t, (i + rotation_t * B) mod N) - value_t) ) / (x_i - z)        in Ext
+ * d_out receives N Ext elements (4 N words, element i at d_out + 4 i) and must be 16-byte aligned.  accumulate != 0 adds
+ * coordinate-wise, so a second matrix is a second call.  A point with x_i = z (possible only when z1 = z2 = z3 = 0) yields 0 for that
+ * point alone.  nterms == 0 writes 4 N zeros, or leaves d_out alone when accumulating.  d_out must not overlap the matrix.  With z, the
+ * weights and the values embedded from the base field, coordinate 0 is toyni_deep_combine_device's word and the others are 0.
+ * The matrix is read as 3e reads it: 16-byte loads where the column's first word is 16-byte aligned and rotation * B is a multiple of
+ * 4 (N >= 4), word loads otherwise.  Up to 64 terms travel inside the kernel's arguments (such a call can be captured into a HIP
+ * graph); a longer table goes through the context's pinned staging ring and per-stream buffer exactly as in 3e.
+ * The division costs one base-field inversion per 4 points: (x - z)^-1 = adj_z(x) / m_z(x), adj_z(x) = prod_{j=1..3} (x - phi^j(z)) with
+ * the conjugates phi^j(z)_k = z_k * zeta^(j k), zeta = 11^((p-1)/4), and m_z = (x - z) adj_z the norm, a quartic with base coefficients. */
+int toyni_deep_combine_ext_device(toyni_ntt_ctx* ctx, const uint32_t* d_values, size_t width, size_t col_stride, unsigned log_blowup,
+                                  uint32_t shift, const uint32_t z[4], const toyni_deep_ext_term* terms, size_t nterms,
+                                  int accumulate, uint32_t* d_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:

@@ -113,6 +113,9 @@ SIGNATURES = {
     # section 3e
     "toyni_poly_eval_batch_device": (c_int, [c_void_p, c_void_p, c_size, c_size, c_size, c_void_p, ctypes.c_uint, c_void_p, c_void_p]),
     "toyni_deep_combine_device": (c_int, [c_void_p, c_void_p, c_size, c_size, ctypes.c_uint, c_u32, c_u32, c_void_p, c_size, c_int, c_void_p, c_void_p]),
+    # section 3h
+    "toyni_poly_eval_ext_batch_device": (c_int, [c_void_p, c_void_p, c_size, c_size, c_size, c_void_p, ctypes.c_uint, c_void_p, c_void_p]),
+    "toyni_deep_combine_ext_device": (c_int, [c_void_p, c_void_p, c_size, c_size, ctypes.c_uint, c_u32, c_void_p, c_void_p, c_size, c_int, c_void_p, c_void_p]),
     # section 3f
     "toyni_air_program_check": (c_int, [c_void_p, c_size, c_void_p]),
     "toyni_air_program_create": (c_int, [c_void_p, c_void_p, c_size, ctypes.POINTER(c_void_p)]),

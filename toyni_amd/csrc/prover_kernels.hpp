@@ -207,6 +207,205 @@ TOYNI_HD void deep_combine_group(const DeepCombineArgs& a, const DeepTerm* terms
     for (int j = 0; j < K; ++j) d[j] = mont_mul(bb_sub(sum[j], a.claim), invR[j]);
 }
 
+// ---- the same under Ext challenges (include/toyni_hip.h 3h): base-field matrix, z and the weights in Ext = F_p[X]/(X^4 - 11) ----
+//   d_i = ( sum_t alpha_t M(column_t, (i + rot_t) mod N) - C ) / (x_i - z)   in Ext,   C = sum_t alpha_t value_t  (host, once)
+// Host-side Ext arithmetic on plain residues (src/ext.rs:178-192), for what a call prepares once.
+constexpr uint32_t EXT_W = 11u;                                     // X^4 = EXT_W
+constexpr uint32_t EXT_W_R = cx_mulmod(EXT_W, BB_R1);              // its Montgomery form
+constexpr uint32_t EXT_ZETA = cx_powmod(EXT_W, (BB_P - 1) / 4);    // X^p = EXT_ZETA X: the Frobenius map scales coordinate k by EXT_ZETA^k
+static_assert(cx_mulmod(EXT_ZETA, EXT_ZETA) == BB_P - 1u, "zeta has order 4");
+inline void ext_mul_host(const uint32_t a[4], const uint32_t b[4], uint32_t r[4]) {
+    uint64_t t[7] = {0, 0, 0, 0, 0, 0, 0};
+    for (int i = 0; i < 4; ++i)
+        for (int j = 0; j < 4; ++j) t[i + j] = (t[i + j] + (uint64_t)bb_mul_host(a[i], b[j])) % BB_P;
+    for (int k = 0; k < 4; ++k) r[k] = (uint32_t)((t[k] + (k < 3 ? (uint64_t)EXT_W * t[k + 4] : 0ull)) % BB_P);
+}
+inline void ext_pow_host(const uint32_t b[4], uint64_t e, uint32_t r[4]) {
+    uint32_t acc[4] = {1u, 0u, 0u, 0u}, sq[4] = {b[0], b[1], b[2], b[3]};
+    for (; e; e >>= 1) {
+        if (e & 1u) ext_mul_host(acc, sq, acc);
+        ext_mul_host(sq, sq, sq);
+    }
+    for (int k = 0; k < 4; ++k) r[k] = acc[k];
+}
+// (x - z)^-1 for BASE x and Ext z behind one BASE inversion.  The conjugates of z are coordinate-wise, phi^j(z)_k = z_k zeta^(j k), so
+//   (x - z)^-1 = adj_z(x) / m_z(x),   adj_z(x) = prod_{j=1..3} (x - phi^j(z))  (a cubic in x, Ext coefficients),
+//                                     m_z(x) = (x - z) adj_z(x)                (the norm: a monic quartic, base coefficients)
+// and m_z(x) = 0 only where x = z.  The host expands both once per z; coefficient i belongs to x^i, the leading ones are 1.
+struct ExtShift {
+    uint32_t adjR[3][4];     // Montgomery forms
+    uint32_t mR[4];
+};
+inline ExtShift ext_shift_host(const uint32_t z[4]) {
+    uint32_t c[3][4], zj = 1u;
+    for (int j = 0; j < 3; ++j) {
+        zj = bb_mul_host(zj, EXT_ZETA);                 // zeta^(j + 1)
+        uint32_t zjk = 1u;
+        for (int k = 0; k < 4; ++k) { c[j][k] = bb_mul_host(z[k], zjk); zjk = bb_mul_host(zjk, zj); }
+    }
+    const auto neg = [](uint32_t v) { return v ? BB_P - v : 0u; };
+    uint32_t a[3][4], c01[4], s01[4], t[4], m[4];
+    ext_mul_host(c[0], c[1], c01);
+    for (int k = 0; k < 4; ++k) s01[k] = (uint32_t)(((uint64_t)c[0][k] + c[1][k]) % BB_P);
+    ext_mul_host(s01, c[2], t);
+    ext_mul_host(c01, c[2], a[0]);
+    for (int k = 0; k < 4; ++k) {
+        a[2][k] = neg((uint32_t)(((uint64_t)s01[k] + c[2][k]) % BB_P));    // -(c1 + c2 + c3)
+        a[1][k] = (uint32_t)(((uint64_t)c01[k] + t[k]) % BB_P);            // c1 c2 + (c1 + c2) c3
+        a[0][k] = neg(a[0][k]);                                           // -c1 c2 c3
+    }
+    // (x - z)(x^3 + a2 x^2 + a1 x + a0): coordinate 0 of each coefficient (the others cancel)
+    m[3] = (uint32_t)(((uint64_t)a[2][0] + neg(z[0])) % BB_P);
+    for (int i = 2; i >= 1; --i) { ext_mul_host(z, a[i], t); m[i] = (uint32_t)(((uint64_t)a[i - 1][0] + neg(t[0])) % BB_P); }
+    ext_mul_host(z, a[0], t);
+    m[0] = neg(t[0]);
+    ExtShift s;
+    for (int i = 0; i < 3; ++i)
+        for (int k = 0; k < 4; ++k) s.adjR[i][k] = to_mont_host(a[i][k]);
+    for (int i = 0; i < 4; ++i) s.mR[i] = to_mont_host(m[i]);
+    return s;
+}
+// invR[j] = (x_j - z)^-1 as four Montgomery forms, for the K base points xR[j] (Montgomery forms): both polynomials by Horner, then ONE
+// Fermat inversion for the K norms (Montgomery's trick, a zero norm kept out of the chain with the marker of deep_point_inverses);
+// all four coordinates 0 where x_j = z.  An Ext LogUp term 1 / (gamma + v) is this with z = -gamma and the column's values as points.
+template <int K>
+TOYNI_HD void ext_shifted_inverses(const ExtShift& s, const uint32_t (&xR)[K], uint32_t (&invR)[K][4]) {
+    uint32_t dR[K], pre[K];
+    uint32_t acc = BB_R1;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            uint32_t t = k ? s.adjR[2][k] : bb_add(s.adjR[2][0], xR[j]);
+            t = bb_add(mont_mul(t, xR[j]), s.adjR[1][k]);
+            invR[j][k] = bb_add(mont_mul(t, xR[j]), s.adjR[0][k]);      // adj_z(x_j), coordinate k
+        }
+        uint32_t m = bb_add(s.mR[3], xR[j]);
+#pragma unroll
+        for (int i = 2; i >= 0; --i) m = bb_add(mont_mul(m, xR[j]), s.mR[i]);
+        dR[j] = m;                                                     // m_z(x_j)
+        if (dR[j] == 0u) dR[j] = BB_R1 | 0x80000000u;                  // marker (never a canonical value)
+        pre[j] = acc;
+        acc = mont_mul(acc, (dR[j] & 0x80000000u) ? BB_R1 : dR[j]);
+    }
+    uint32_t inv = mont_inv(acc);
+#pragma unroll
+    for (int j = K - 1; j >= 0; --j) {
+        const bool zero = (dR[j] & 0x80000000u) != 0u;
+        const uint32_t mi = zero ? 0u : mont_mul(inv, pre[j]);        // m_z(x_j)^-1 R
+        if (!zero) inv = mont_mul(inv, dR[j]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) invR[j][k] = mont_mul(invR[j][k], mi);
+    }
+}
+// One table entry per term, 32 bytes, sorted by (column, rot) on the host as the base table is
+struct alignas(16) DeepExtTerm {
+    uint32_t column;
+    uint32_t rot;            // rotation * B: the distance in words, < N
+    uint32_t alphaR[4];      // Montgomery forms of the weight's coordinates
+    uint32_t pad[2];
+};
+struct DeepExtArgs {
+    const uint32_t* values;  // element (i, c) at values[c * col_stride + i]: base field
+    uint32_t* out;           // N Ext elements, four consecutive words each; 16-byte aligned
+    uint64_t col_stride;
+    DomainArgs dom;
+    uint32_t log_N, nterms;
+    uint32_t wNR;            // Montgomery form of w_N
+    uint32_t accumulate;
+    uint32_t claim[4];       // C, plain
+    ExtShift shift;          // adj_z and m_z
+};
+// the K words of one term for the points i0 .. i0 + K - 1 (i0 a multiple of K; N a multiple of K): one 16-byte load where the column's
+// first word is 16-byte aligned and the rotation a multiple of 4 (the quad then lies inside the column), word loads otherwise
+template <int K>
+TOYNI_HD void deep_ext_term_load(const DeepExtArgs& a, const uint32_t column, const uint32_t rot, uint64_t i0, uint32_t (&v)[K]) {
+    const uint64_t mask = ((uint64_t)1 << a.log_N) - 1;
+    const uint32_t* col = a.values + (uint64_t)column * a.col_stride;
+    if (K == 4 && !(((uintptr_t)col & 15) | (rot & 3u))) {
+        const DeepQuad q = *reinterpret_cast<const DeepQuad*>(col + ((i0 + rot) & mask));
+#pragma unroll
+        for (int j = 0; j < K; ++j) v[j] = q[j & 3];
+    } else {
+#pragma unroll
+        for (int j = 0; j < K; ++j) v[j] = col[(i0 + (uint64_t)j + rot) & mask];
+    }
+}
+// entry t of the table: the same in every lane, so scalar registers and uniform branches
+TOYNI_HD DeepExtTerm deep_ext_term_at(const DeepExtTerm* terms, uint32_t t) {
+    return DeepExtTerm{TOYNI_UNIFORM(terms[t].column), TOYNI_UNIFORM(terms[t].rot),
+                       {TOYNI_UNIFORM(terms[t].alphaR[0]), TOYNI_UNIFORM(terms[t].alphaR[1]), TOYNI_UNIFORM(terms[t].alphaR[2]),
+                        TOYNI_UNIFORM(terms[t].alphaR[3])}, {0u, 0u}};
+}
+// Per term and point four multiply-adds, one per coordinate of the weight, into 64-bit accumulators; four terms share a reduction as in
+// deep_combine_group.  Then (S_j - C) * (x_j - z)^-1 as one Ext product by the point's inverse (ext_mul: the right factor in
+// Montgomery form with its multiples of 11).  d[j]: the four plain coordinates of point i0 + j.
+template <int K>
+TOYNI_HD void deep_combine_ext_group(const DeepExtArgs& a, const DeepExtTerm* terms, uint64_t i0, uint32_t (&d)[K][4]) {
+    uint32_t sum[K][4];
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sum[j][k] = 0u;
+    uint32_t t = 0;
+    for (; t + 4 <= a.nterms; t += 4) {
+        uint64_t acc[K][4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const DeepExtTerm tm = deep_ext_term_at(terms, t + q);
+            uint32_t v[K];
+            deep_ext_term_load<K>(a, tm.column, tm.rot, i0, v);
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[j][k] = (q ? acc[j][k] : 0ull) + (uint64_t)v[j] * tm.alphaR[k];
+        }
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sum[j][k] = bb_add(sum[j][k], mont_reduce_wide(acc[j][k]));
+    }
+    if (t < a.nterms) {   // one to three terms left
+        uint64_t acc[K][4];
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[j][k] = 0ull;
+        for (; t < a.nterms; ++t) {
+            const DeepExtTerm tm = deep_ext_term_at(terms, t);
+            uint32_t v[K];
+            deep_ext_term_load<K>(a, tm.column, tm.rot, i0, v);
+#pragma unroll
+            for (int j = 0; j < K; ++j)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[j][k] += (uint64_t)v[j] * tm.alphaR[k];
+        }
+#pragma unroll
+        for (int j = 0; j < K; ++j)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) sum[j][k] = bb_add(sum[j][k], mont_reduce_wide(acc[j][k]));
+    }
+    uint32_t xR[K], invR[K][4];
+    xR[0] = domain_point_mont(a.dom, i0);
+#pragma unroll
+    for (int j = 1; j < K; ++j) xR[j] = mont_mul(xR[j - 1], a.wNR);
+    ext_shifted_inverses<K>(a.shift, xR, invR);
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+        Ext4 s;
+        ExtFactor f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            s.c[k] = bb_sub(sum[j][k], a.claim[k]);
+            f.b[k] = invR[j][k];
+            f.b11[k] = mont_mul(invR[j][k], EXT_W_R);
+        }
+        const Ext4 r = ext_mul(s, f);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) d[j][k] = r.c[k];
+    }
+}
+
 // ---- constraint programs of any AIR over up to four column-major matrices (include/toyni_hip.h 3f) ----
 //   c_i = sum_{EMIT k, b = 0} weights[k] value_k(i),   q_i = c_i / (x_i^n - 1) + sum_{EMIT k, b = 1} weights[k] value_k(i)
 // A straight-line program, the same in every lane, is interpreted once per group of K consecutive points.  Its registers hold
@@ -571,6 +770,72 @@ TOYNI_HD uint32_t poly_batch_final_thread(const PolyBatchArgs& a, uint32_t col, 
     for (uint32_t b = t; b < a.e.nblocks; b += nthreads)
         acc = bb_add(acc, mont_mul(a.e.partial[poly_batch_partial_index(a, col, b, p)], mont_pow(a.e.zchunkR[p], b)));
     return acc;
+}
+
+// The same at Ext points (include/toyni_hip.h 3h): base coefficients, Ext values.  Every product is an ext_mul by a factor the host
+// prepared: the Horner step by the point itself, the powers z^(16 t) and (z^POLY_CHUNK)^chunk from a table of squarings that rides in
+// the kernel arguments (one bit of the thread's or chunk's index per entry).
+constexpr int POLY_EXT_BITS = 8;                 // POLY_THREADS = 2^8: the bits of a thread's index, and of a chunk's index within a stride
+static_assert((1u << POLY_EXT_BITS) == POLY_THREADS, "one squaring per bit of the thread index");
+struct PolyExtPowers {
+    ExtFactor step;                              // stage 1: z                  stage 2: (z^POLY_CHUNK)^POLY_THREADS
+    ExtFactor sq[POLY_EXT_BITS];                 // stage 1: (z^16)^(2^i)       stage 2: (z^POLY_CHUNK)^(2^i)
+};
+inline PolyExtPowers poly_ext_powers_host(const uint32_t step[4], const uint32_t base[4]) {
+    PolyExtPowers pw;
+    pw.step = ext_factor_host(step);
+    uint32_t s[4] = {base[0], base[1], base[2], base[3]};
+    for (int i = 0; i < POLY_EXT_BITS; ++i) { pw.sq[i] = ext_factor_host(s); ext_mul_host(s, s, s); }
+    return pw;
+}
+struct PolyExtArgs {
+    const uint32_t* coeffs;                      // column 0; column b starts b * stride words on
+    uint64_t ncoeffs, stride;
+    uint32_t batch, npoints, nblocks;
+    uint32_t* partial;                           // [column][chunk][point][4]
+    uint32_t* out;                               // [column][point][4]
+    PolyExtPowers thread[POLY_MAX_POINTS], chunk[POLY_MAX_POINTS];
+};
+TOYNI_HD void poly_ext_load(const PolyExtArgs& a, uint32_t col, uint32_t chunk, uint32_t t, uint32_t (&c)[POLY_PER_THREAD]) {
+    const uint32_t* src = a.coeffs + (uint64_t)col * a.stride;
+    const uint64_t base = (uint64_t)chunk * POLY_CHUNK + (uint64_t)t * POLY_PER_THREAD;
+#pragma unroll
+    for (uint32_t j = 0; j < POLY_PER_THREAD; ++j) c[j] = base + j < a.ncoeffs ? src[base + j] : 0u;
+}
+TOYNI_HD uint64_t poly_ext_partial_index(const PolyExtArgs& a, uint32_t col, uint32_t chunk, uint32_t p) {
+    return (((uint64_t)col * a.nblocks + chunk) * a.npoints + p) * 4u;
+}
+// r * base^e for e < POLY_THREADS, base^(2^i) = pw.sq[i]
+TOYNI_HD Ext4 poly_ext_times_power(const PolyExtPowers& pw, Ext4 r, uint32_t e) {
+#pragma unroll
+    for (int i = 0; i < POLY_EXT_BITS; ++i)
+        if ((e >> i) & 1u) r = ext_mul(r, pw.sq[i]);
+    return r;
+}
+// the 16 coefficients of one thread: sum_j c_j z^j by Horner (the coefficient enters coordinate 0), then times z^(16 t)
+TOYNI_HD Ext4 poly_ext_thread_term(const PolyExtArgs& a, uint32_t p, const uint32_t (&c)[POLY_PER_THREAD], uint32_t t) {
+    const PolyExtPowers& pw = a.thread[p];
+    Ext4 r = {{c[POLY_PER_THREAD - 1], 0u, 0u, 0u}};
+#pragma unroll
+    for (int j = (int)POLY_PER_THREAD - 2; j >= 0; --j) {
+        r = ext_mul(r, pw.step);
+        r.c[0] = bb_add(r.c[0], c[j]);
+    }
+    return poly_ext_times_power(pw, r, t);
+}
+// stage 2, thread t of POLY_THREADS: its share of sum_chunk partial[col][chunk][p] * (z^POLY_CHUNK)^chunk -- the chunks t, t + 256, ...
+// by Horner in (z^POLY_CHUNK)^256 from the last one down, then times (z^POLY_CHUNK)^t
+TOYNI_HD Ext4 poly_ext_final_thread(const PolyExtArgs& a, uint32_t col, uint32_t p, uint32_t t) {
+    const PolyExtPowers& pw = a.chunk[p];
+    Ext4 r = {{0u, 0u, 0u, 0u}};
+    if (t >= a.nblocks) return r;
+    for (uint32_t k = (a.nblocks - 1u - t) / POLY_THREADS + 1u; k-- > 0u;) {
+        const uint32_t* w = a.partial + poly_ext_partial_index(a, col, t + k * POLY_THREADS, p);
+        r = ext_mul(r, pw.step);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) r.c[q] = bb_add(r.c[q], w[q]);
+    }
+    return poly_ext_times_power(pw, r, t);
 }
 
 // ---- Merkle openings (src/merkle.rs:50-80, src/fibonacci.rs:366-375) ----

@@ -771,6 +771,72 @@ constexpr uint32_t DEEP_INLINE_TERMS = 64;
 struct DeepInlineTerms { DeepTerm t[DEEP_INLINE_TERMS]; };
 __global__ void __launch_bounds__(256) deep_combine_inline_kernel(const DeepCombineArgs a, const DeepInlineTerms in) { deep_combine_body(a, in.t); }
 
+// The same under Ext challenges (include/toyni_hip.h 3h): one group of 4 consecutive points per thread -- four Ext elements, four
+// 16-byte stores (the output is 16-byte aligned by contract) -- and single points below N = 4.  No grid-stride loop, as above.
+__device__ __forceinline__ void deep_combine_ext_body(const DeepExtArgs& a, const DeepExtTerm* terms) {
+    constexpr int K = 4;
+    const uint64_t N = (uint64_t)1 << a.log_N;
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a.log_N >= 2) {
+        if (g >= N / K) return;
+        uint32_t d[K][4];
+        deep_combine_ext_group<K>(a, terms, g * K, d);
+        uint4* o = reinterpret_cast<uint4*>(a.out) + g * K;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if (a.accumulate) {
+                const uint4 p = o[j];
+                o[j] = make_uint4(bb_add(p.x, d[j][0]), bb_add(p.y, d[j][1]), bb_add(p.z, d[j][2]), bb_add(p.w, d[j][3]));
+            } else {
+                o[j] = make_uint4(d[j][0], d[j][1], d[j][2], d[j][3]);
+            }
+        }
+    } else if (g < N) {
+        uint32_t d[1][4];
+        deep_combine_ext_group<1>(a, terms, g, d);
+        uint4* o = reinterpret_cast<uint4*>(a.out) + g;
+        const uint4 p = a.accumulate ? o[0] : make_uint4(0u, 0u, 0u, 0u);
+        o[0] = make_uint4(bb_add(p.x, d[0][0]), bb_add(p.y, d[0][1]), bb_add(p.z, d[0][2]), bb_add(p.w, d[0][3]));
+    }
+}
+__global__ void __launch_bounds__(256) deep_combine_ext_kernel(const DeepExtArgs a, const DeepExtTerm* __restrict__ terms) { deep_combine_ext_body(a, terms); }
+// up to DEEP_EXT_INLINE_TERMS entries of 32 bytes inside the kernel arguments (2 KiB): capturable, no copy ahead of the launch
+constexpr uint32_t DEEP_EXT_INLINE_TERMS = 64;
+struct DeepExtInlineTerms { DeepExtTerm t[DEEP_EXT_INLINE_TERMS]; };
+__global__ void __launch_bounds__(256) deep_combine_ext_inline_kernel(const DeepExtArgs a, const DeepExtInlineTerms in) { deep_combine_ext_body(a, in.t); }
+
+// Polynomial evaluation at Ext points, the two stages of the batched form above; block_sum_mod runs once per coordinate
+__global__ void __launch_bounds__(256) poly_eval_ext_batch_partial_kernel(const PolyExtArgs a) {
+    __shared__ uint32_t red[256];
+    for (uint32_t col = blockIdx.y; col < a.batch; col += gridDim.y) {
+        uint32_t c[POLY_PER_THREAD];
+        poly_ext_load(a, col, blockIdx.x, threadIdx.x, c);
+        for (uint32_t p = 0; p < a.npoints; ++p) {
+            const Ext4 v = poly_ext_thread_term(a, p, c, threadIdx.x);
+            uint32_t* dst = a.partial + poly_ext_partial_index(a, col, blockIdx.x, p);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t sum = block_sum_mod(v.c[k], red);
+                if (threadIdx.x == 0) dst[k] = sum;
+            }
+        }
+    }
+}
+// one block per column
+__global__ void __launch_bounds__(256) poly_eval_ext_batch_final_kernel(const PolyExtArgs a) {
+    __shared__ uint32_t red[256];
+    for (uint32_t col = blockIdx.x; col < a.batch; col += gridDim.x)
+        for (uint32_t p = 0; p < a.npoints; ++p) {
+            const Ext4 v = poly_ext_final_thread(a, col, p, threadIdx.x);
+            uint32_t* dst = a.out + ((uint64_t)col * a.npoints + p) * 4u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t sum = block_sum_mod(v.c[k], red);
+                if (threadIdx.x == 0) dst[k] = sum;
+            }
+        }
+}
+
 // Constraint program of an AIR (prover_kernels.hpp): one group of 4 consecutive points per thread, single points below N = 4.  No
 // grid-stride loop: every read of the program and of the weights precedes the thread's only global stores, so both are fetched
 // by scalar loads.  Dynamic LDS: [nregs][threads] slots of 16 bytes (the register file, sized from the program), then 1 / Z_H of
@@ -3169,6 +3235,107 @@ int toyni_deep_combine_device(toyni_ntt_ctx* c, const uint32_t* d_values, size_t
     std::memcpy(h, table.data(), nterms * sizeof(DeepTerm));
     HIPCHK(hipMemcpyAsync(sc.d_lde32, h, nterms * sizeof(DeepTerm), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(deep_combine_kernel, grid, dim3(256), 0, s, a, reinterpret_cast<const DeepTerm*>(sc.d_lde32));
+    return (int)hipGetLastError();
+}
+
+// ---- section 3h: the same two steps under Ext challenges ----
+static bool ext_canonical(const uint32_t v[4]) { return v[0] < BB_P && v[1] < BB_P && v[2] < BB_P && v[3] < BB_P; }
+
+int toyni_poly_eval_ext_batch_device(toyni_ntt_ctx* c, const uint32_t* d_coeffs, size_t ncoeffs, size_t stride, size_t batch, const uint32_t* points,
+                                     unsigned npoints, uint32_t* d_out, void* stream) {
+    if (!c || !points || !d_out || (!d_coeffs && ncoeffs)) return TOYNI_E_NULL;
+    if (npoints < 1 || npoints > (unsigned)POLY_MAX_POINTS) return TOYNI_E_RANGE;
+    for (unsigned p = 0; p < npoints; ++p) if (!ext_canonical(points + 4 * p)) return TOYNI_E_RANGE;
+    if ((batch > 1 && stride < ncoeffs) || batch > 0xFFFFFFFFull || (((uintptr_t)d_coeffs | (uintptr_t)d_out) & 3)) return TOYNI_E_RANGE;
+    if (batch == 0) return TOYNI_OK;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (ncoeffs == 0) return (int)hipMemsetAsync(d_out, 0, batch * npoints * 4 * sizeof(uint32_t), s);   // zero polynomials
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    PolyExtArgs a{};
+    a.coeffs = d_coeffs;
+    a.ncoeffs = ncoeffs;
+    a.stride = stride;
+    a.batch = (uint32_t)batch;
+    a.npoints = npoints;
+    a.nblocks = (uint32_t)((ncoeffs + POLY_CHUNK - 1) / POLY_CHUNK);
+    int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words, batch * a.nblocks * npoints * 4, sizeof(uint32_t));
+    if (rc) return rc;
+    a.partial = sc.d_lde32;
+    a.out = d_out;
+    for (unsigned p = 0; p < npoints; ++p) {
+        uint32_t z16[4], zchunk[4], zstride[4];
+        ext_pow_host(points + 4 * p, POLY_PER_THREAD, z16);
+        ext_pow_host(points + 4 * p, POLY_CHUNK, zchunk);
+        ext_pow_host(zchunk, POLY_THREADS, zstride);
+        a.thread[p] = poly_ext_powers_host(points + 4 * p, z16);
+        a.chunk[p] = poly_ext_powers_host(zstride, zchunk);
+    }
+    const unsigned rows = (unsigned)std::min<size_t>(batch, 65535);
+    hipLaunchKernelGGL(poly_eval_ext_batch_partial_kernel, dim3(a.nblocks, rows), dim3(POLY_THREADS), 0, s, a);
+    hipLaunchKernelGGL(poly_eval_ext_batch_final_kernel, dim3(rows), dim3(POLY_THREADS), 0, s, a);
+    return (int)hipGetLastError();
+}
+
+int toyni_deep_combine_ext_device(toyni_ntt_ctx* c, const uint32_t* d_values, size_t width, size_t col_stride, unsigned log_blowup, uint32_t shift,
+                                  const uint32_t z[4], const toyni_deep_ext_term* terms, size_t nterms, int accumulate, uint32_t* d_out,
+                                  void* stream) {
+    if (!c || !d_values || !d_out || !z || (!terms && nterms)) return TOYNI_E_NULL;
+    const int log_N = c->plan.log_n;
+    const uint64_t N = 1ull << log_N;
+    if ((int)log_blowup > log_N || shift == 0 || shift >= BB_P || !ext_canonical(z) || width == 0 || width > 65536 || col_stride < N ||
+        nterms > ((size_t)1 << 20) || ((uintptr_t)d_values & 3) || ((uintptr_t)d_out & 15))
+        return TOYNI_E_RANGE;
+    for (size_t t = 0; t < nterms; ++t)
+        if (terms[t].column >= width || terms[t].rotation >= (N >> log_blowup) || !ext_canonical(terms[t].alpha) || !ext_canonical(terms[t].value))
+            return TOYNI_E_RANGE;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (nterms == 0) return accumulate ? TOYNI_OK : (int)hipMemsetAsync(d_out, 0, N * 4 * sizeof(uint32_t), s);
+    // the table the kernel reads, sorted by (column, rotation) as the base call's is; the claimed values collapse into one Ext constant
+    std::vector<DeepExtTerm> table(nterms);
+    DeepExtArgs a{};
+    for (size_t t = 0; t < nterms; ++t) {
+        DeepExtTerm& e = table[t];
+        e = DeepExtTerm{};
+        e.column = terms[t].column;
+        e.rot = (uint32_t)((uint64_t)terms[t].rotation << log_blowup);
+        uint32_t av[4];
+        ext_mul_host(terms[t].alpha, terms[t].value, av);
+        for (int k = 0; k < 4; ++k) {
+            e.alphaR[k] = to_mont_host(terms[t].alpha[k]);
+            a.claim[k] = (uint32_t)(((uint64_t)a.claim[k] + av[k]) % BB_P);
+        }
+    }
+    std::stable_sort(table.begin(), table.end(), [](const DeepExtTerm& x, const DeepExtTerm& y) { return x.column != y.column ? x.column < y.column : x.rot < y.rot; });
+    a.values = d_values;
+    a.out = d_out;
+    a.col_stride = col_stride;
+    a.dom = domain_args(c, (unsigned)log_N, shift);
+    a.log_N = (uint32_t)log_N;
+    a.nterms = (uint32_t)nterms;
+    a.wNR = to_mont_host(bb_root_of_unity_host((uint32_t)log_N));
+    a.accumulate = accumulate ? 1u : 0u;
+    a.shift = ext_shift_host(z);
+    const uint64_t items = log_N >= 2 ? N / 4 : N;
+    const dim3 grid((unsigned)((items + 255) / 256));
+    if (nterms <= DEEP_EXT_INLINE_TERMS) {   // the table rides in the kernel arguments
+        DeepExtInlineTerms in{};
+        std::copy(table.begin(), table.end(), in.t);
+        hipLaunchKernelGGL(deep_combine_ext_inline_kernel, grid, dim3(256), 0, s, a, in);
+        return (int)hipGetLastError();
+    }
+    // a longer table: pinned staging ring -> the stream's intermediate buffer by a stream-ordered copy, as toyni_deep_combine_device
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words, nterms * (sizeof(DeepExtTerm) / sizeof(uint32_t)), sizeof(uint32_t));
+    if (rc) return rc;
+    void* h = nullptr;
+    if ((rc = ring_slice(sc, s, nterms * sizeof(DeepExtTerm), &h))) return rc;
+    std::memcpy(h, table.data(), nterms * sizeof(DeepExtTerm));
+    HIPCHK(hipMemcpyAsync(sc.d_lde32, h, nterms * sizeof(DeepExtTerm), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(deep_combine_ext_kernel, grid, dim3(256), 0, s, a, reinterpret_cast<const DeepExtTerm*>(sc.d_lde32));
     return (int)hipGetLastError();
 }
 

@@ -91,6 +91,40 @@ def deep_combine_device(ctx, d_values: int, width: int, col_stride: int, log_blo
                                         1 if accumulate else 0, d_out, stream or None), "GPU DEEP combination failed")
 
 
+def poly_eval_ext_batch_device(ctx, d_coeffs: int, ncoeffs: int, stride: int, batch: int, points4, d_out: int, stream: int = 0) -> None:
+    """d_out[(b * npoints + p) * 4 + k] = coordinate k of column b (base-field coefficients) evaluated at the Ext point points4[p]
+    (npoints x 4 words): the out-of-domain values under Ext challenges (include/toyni_hip.h 3h)."""
+    p = np.ascontiguousarray(points4, dtype=np.uint32).reshape(-1, 4)
+    check(lib.toyni_poly_eval_ext_batch_device(ctx.handle, d_coeffs or None, ncoeffs, stride, batch, p.ctypes.data, p.shape[0], d_out, stream or None),
+          "GPU batched Ext polynomial evaluation failed")
+
+
+class DeepExtTerm(ctypes.Structure):   # toyni_deep_ext_term (include/toyni_hip.h 3h)
+    _fields_ = [("column", ctypes.c_uint32), ("rotation", ctypes.c_uint32), ("alpha", ctypes.c_uint32 * 4), ("value", ctypes.c_uint32 * 4)]
+
+
+def deep_ext_terms(columns, rotations, alphas4, values4):
+    """The term table of deep_combine_ext_device: term t weighs column columns[t], read rotations[t] trace rows ahead, by the Ext
+    weight alphas4[t] against the claimed Ext value values4[t] (four coordinates each)."""
+    cols, rots = (np.asarray(v, dtype=np.uint32).ravel() for v in (columns, rotations))
+    als, vals = (np.asarray(v, dtype=np.uint32).reshape(-1, 4) for v in (alphas4, values4))
+    assert cols.size == rots.size == als.shape[0] == vals.shape[0]
+    U4 = ctypes.c_uint32 * 4
+    return (DeepExtTerm * cols.size)(*[DeepExtTerm(int(c), int(r), U4(*map(int, a)), U4(*map(int, v))) for c, r, a, v in zip(cols, rots, als, vals)])
+
+
+def deep_combine_ext_device(ctx, d_values: int, width: int, col_stride: int, log_blowup: int, shift: int, z4, terms, d_out: int,
+                            accumulate: bool = False, stream: int = 0) -> None:
+    """d_out[4 i .. 4 i + 3] (+)= sum_t alpha_t (M(column_t, i + rotation_t B) - value_t) / (x_i - z) in Ext over a base-field
+    column-major matrix on the LDE coset (include/toyni_hip.h 3h).  z4: four coordinates; terms: what deep_ext_terms returns;
+    d_out: 16-byte aligned."""
+    z = np.ascontiguousarray(z4, dtype=np.uint32)
+    assert z.size == 4
+    check(lib.toyni_deep_combine_ext_device(ctx.handle, d_values, width, col_stride, log_blowup, shift, z.ctypes.data,
+                                            terms if len(terms) else None, len(terms), 1 if accumulate else 0, d_out, stream or None),
+          "GPU Ext DEEP combination failed")
+
+
 # ---- constraint programs (include/toyni_hip.h 3f) ----
 AIR_CELL, AIR_CONST, AIR_X, AIR_XINV, AIR_ADD, AIR_SUB, AIR_MUL, AIR_EMIT = range(8)
 AIR_MAX_REGS, AIR_MAX_MATRICES = 64, 4
