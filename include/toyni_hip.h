@@ -314,6 +314,7 @@ int toyni_merkle_open_rows_device(const uint8_t* d_levels, size_t n, const uint3
  *     stays on the device; the AIR's constraint evaluation between the commitment and the quotient is 3f.  A staged AIR adds one stage
  *     after the main columns' commitment: the per-row terms from a 3f program at log_blowup = 0 -> toyni_column_scan_device (3g) -> the
  *     accumulator columns through the same inverse transform, toyni_lde_device and toyni_merkle_commit_rows_device as a second matrix.
+ *     Under an Ext challenge gamma that stage is toyni_column_scan_ext_device (3i): each accumulator is four base columns of that matrix.
  *     Both calls are asynchronous on `stream`, take packed-u32 canonical residues and write canonical residues.  Device pointers are
  *     4-byte aligned.  `points` and `terms` are host arrays that the caller may reuse as soon as the call returns.  Both calls may use the
  *     context's per-stream intermediate buffer (calls on one stream run in order; use one stream per concurrent call).
@@ -471,8 +472,8 @@ int toyni_column_scan_device(toyni_ntt_ctx* ctx, const uint32_t* d_num, size_t n
  *         -> toyni_fri_fold_ext_device / toyni_merkle_commit_rows_device(TOYNI_ROWS_ROW_MAJOR, width = 4) per round
  *     stays on the device.  The quotient under Ext weights needs nothing new: toyni_air_quotient_device is linear in its weights, so
  *     four calls with the coordinates of the weights write the quotient's four base columns, which join the DEEP combination as a
- *     second matrix (accumulate).  An Ext-valued polynomial held as four base columns q_0..q_3 (that quotient, later an Ext
- *     accumulator) needs no entry point of its own either: evaluate the four columns here and combine on the host,
+ *     second matrix (accumulate).  An Ext-valued polynomial held as four base columns q_0..q_3 (that quotient, or an Ext
+ *     accumulator of 3i) needs no entry point of its own either: evaluate the four columns here and combine on the host,
  *     q(z) = sum_j X^j q_j(z).
  *     Ext = F_p[X]/(X^4 - 11), four consecutive words c0..c3 (section 3).  Every convention is that of 3e: asynchronous on `stream`,
  *     packed-u32 canonical residues in and out, `points`, `z` and `terms` are host arrays that the caller may reuse as soon as the call
@@ -502,6 +503,57 @@ typedef struct { uint32_t column, rotation; uint32_t alpha[4]; uint32_t value[4]
 int toyni_deep_combine_ext_device(toyni_ntt_ctx* ctx, const uint32_t* d_values, size_t width, size_t col_stride, unsigned log_blowup,
                                   uint32_t shift, const uint32_t z[4], const toyni_deep_ext_term* terms, size_t nterms,
                                   int accumulate, uint32_t* d_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 3i. The accumulator columns of 3g under an Ext challenge: the permutation product and the LogUp sum with gamma in Ext (about 124
+ *     bits instead of 31), so that the staged AIR of 3g lives in the protocol shape of 3h.  The accumulator is then an Ext-valued
+ *     column and its terms are Ext quotients.  With it the sequence for a staged AIR
+ *         committed main columns -> toyni_column_scan_ext_device -> the 4 x batch base columns through the batched inverse transform,
+ *         toyni_lde_device and toyni_merkle_commit_rows_device as a second matrix -> toyni_air_quotient_device under Ext weights (four
+ *         calls) -> toyni_poly_eval_ext_batch_device -> toyni_deep_combine_ext_device
+ *     stays on the device.
+ *     Layout: an Ext column is FOUR base columns, one per coordinate: coordinate k of element i of Ext column b is at
+ *     ptr[(4 b + k) * stride + i], stride >= n, packed-u32 canonical residues -- what four 3f calls with the coordinates of Ext weights
+ *     write, what the batched transforms and the column-major row commitment read, and what 3h calls an Ext polynomial held as four
+ *     base columns.
+ *     Semantics: those of 3g with every value in Ext.  term_i = num_i / den_i; where den_i = 0 (all four coordinates) term_i = 0 and
+ *     the zero is counted;  out[0] = init[b];  out[i] = out[i-1] (+ or *) term_{i-1};  d_totals[8 b .. 8 b + 3] = the wrap-around value
+ *     out[n-1] (+ or *) term_{n-1},  d_totals[8 b + 4] = the zero denominators met,  d_totals[8 b + 5 .. 8 b + 7] = 0.
+ *     Forms: the permutation argument z * (gamma + a_i) / (gamma + b_i) is two width-1 operands with shift = gamma; LogUp
+ *     m_i / (gamma + t_i) is a width-1 numerator with shift 0 and a width-1 denominator with shift gamma; arguments over several
+ *     columns combined under Ext weights use width-4 operands (four 3f calls: 3f is linear in its weights).
+ *     Size: 1 <= n <= 2^27, any n; batch < 2^14; n == 0 or batch == 0 succeeds and writes nothing.  n is NOT tied to the context's size:
+ *     the context lends its device, its lock and its per-stream intermediate buffer (5 words per tile and column).
+ *     Asynchronous on `stream`.  Exactness: Ext is a commutative field, so every evaluation order gives the same words, at every launch
+ *     shape.  In place: d_out may be exactly a width-4 operand's d_values with the same stride; any other overlap is the caller's error.
+ *     Loads and stores: 16 bytes at a time where a coordinate column's first word is 16-byte aligned, word accesses otherwise; the result
+ *     is the same.  The words between n and a stride are neither read nor written.
+ *     Refused before anything is enqueued, the outputs and the context untouched -- TOYNI_E_NULL for a null ctx, d_out or init;
+ *     TOYNI_E_RANGE for: both operands absent; a width not in {0, 1, 4}; width > 0 with null d_values; an unknown op; n > 2^27; an operand
+ *     stride < n where more than one base column is addressed (width 4, or batch > 1); out_stride < n; batch >= 2^14; an init or shift
+ *     coordinate >= p; a device pointer that is not 4-byte aligned.
+ *     The launches are those of 3g (per-tile aggregates; one workgroup per column scanning them in rounds; the scan inside each tile;
+ *     one launch for n <= one tile), no workgroup waits for another.  Seeds and shifts travel inside the kernel arguments, 16 Ext
+ *     columns to a launch sequence, so a call on a warm context only enqueues kernels and can be captured into a HIP graph (with the
+ *     caveat of section 4).  A width-1 denominator costs one base inversion per 4 elements through the norm form of 3h (z = -shift, the
+ *     column's values as points); a width-4 denominator one per 4 elements through the tower F_p < F_p[Y]/(Y^2 - 11) < Ext, Y = X^2:
+ *     a = A0 + A1 X,  B = A0^2 - Y A1^2 = B0 + B1 Y,  N = B0^2 - 11 B1^2,  a^-1 = (A0 - A1 X)(B0 - B1 Y) / N,  N = 0 only for a = 0.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct { const uint32_t* d_values; size_t stride; uint32_t width; uint32_t shift[4]; } toyni_ext_operand;
+/* element i of column b of an operand:
+ *   width 4: shift + (d_values[(4 b + k) * stride + i])_k       an Ext column
+ *   width 1: shift + embed(d_values[b * stride + i])            a base column plus an Ext constant: gamma + v_i
+ *   width 0 (or a NULL operand pointer): the constant 1; the other fields are ignored                         */
+size_t toyni_column_scan_ext_tile(void);  /* elements one workgroup owns (a power of two): n <= this takes the single launch */
+/* init: host array of batch x 4 canonical residues, reusable on return, as the operands are.  d_totals: batch x 8 words, may be NULL. */
+int toyni_column_scan_ext_device(toyni_ntt_ctx* ctx, const toyni_ext_operand* num, const toyni_ext_operand* den, uint32_t* d_out,
+                                 size_t out_stride, size_t n, size_t batch, int op, const uint32_t* init, uint32_t* d_totals, void* stream);
+/* out_i = in_i^-1 in Ext, and 0 for 0, counted into *d_zero_count (may be NULL; cleared by a stream-ordered fill ahead of the kernel).
+ * The input and the output are each ONE Ext column of `count` elements (four base columns in_stride / out_stride apart, strides >=
+ * count).  d_out == d_in is allowed with equal strides.  No context: the current device.  TOYNI_E_NULL for a null d_in or d_out;
+ * TOYNI_E_RANGE for count > 2^32, a stride < count or a pointer that is not 4-byte aligned.  count == 0 succeeds (and clears the count). */
+int toyni_batch_inverse_ext_device(const uint32_t* d_in, size_t in_stride, uint32_t* d_out, size_t out_stride, size_t count,
+                                   uint32_t* d_zero_count, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:

@@ -128,6 +128,10 @@ SIGNATURES = {
     "toyni_batch_inverse_device": (c_int, [c_void_p, c_void_p, c_size, c_void_p, c_void_p]),
     "toyni_column_scan_device": (c_int, [c_void_p, c_void_p, c_size, c_void_p, c_size, c_void_p, c_size, c_size, c_size, c_int, c_void_p,
                                          c_void_p, c_void_p]),
+    # section 3i
+    "toyni_column_scan_ext_tile": (c_size, []),
+    "toyni_column_scan_ext_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_size, c_size, c_int, c_void_p, c_void_p, c_void_p]),
+    "toyni_batch_inverse_ext_device": (c_int, [c_void_p, c_size, c_void_p, c_size, c_size, c_void_p, c_void_p]),
     # section 3c
     "toyni_fri_fold_commit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

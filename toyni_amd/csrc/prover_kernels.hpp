@@ -726,6 +726,236 @@ TOYNI_HD void scan_group_finish(uint32_t base, const uint32_t (&ex)[G], uint32_t
     for (int j = 0; j < G; ++j) o[j] = scan_to_plain<OP>(scan_combine<OP>(base, ex[j]));
 }
 
+// ---- accumulator columns under an Ext challenge (include/toyni_hip.h 3i) ----
+// The recurrence and the three launches of 3g with every value in Ext = F_p[X]/(X^4 - 11); Ext is a commutative field, so every
+// partial result is exact whatever the order.  An Ext column is FOUR base columns: coordinate k of element i of column b at
+// values[(4 b + k) * stride + i].  Sums run coordinate-wise on plain residues; products on Montgomery forms, one general Ext x Ext
+// product per step.  A thread owns EXT_ACCUM_GROUP consecutive elements (16 words of terms and 16 of running values: no scratch).
+constexpr uint32_t EXT_ACCUM_GROUP = 4, EXT_ACCUM_THREADS = 256, EXT_ACCUM_TILE = EXT_ACCUM_GROUP * EXT_ACCUM_THREADS;
+constexpr uint32_t EXT_ACCUM_INLINE_COLUMNS = 16;   // Ext columns of one launch sequence: their seeds ride in the kernel arguments
+constexpr uint32_t EXT_ACCUM_TILE_WORDS = 5;        // per tile and column: four aggregate coordinates and a zero count
+struct ExtAccumOperand {
+    const uint32_t* values;  // column 0 (null with width 0)
+    uint64_t stride;
+    uint32_t width;          // 4: an Ext column; 1: a base column; 0: the constant 1
+    uint32_t shift[4];       // plain: added to every element
+};
+struct ExtAccumArgs {
+    ExtAccumOperand num, den;
+    ExtShift den_inv;        // a width-1 denominator: 1 / (shift + v) = 1 / (v - z), z = -shift (ext_shift_host)
+    uint32_t* out;           // Ext columns
+    uint64_t out_stride;
+    uint64_t n;
+    uint32_t* tiles;         // column b: an Ext column of ntiles aggregates (step 2 turns them into prefixes in place), then ntiles zero counts
+    uint32_t* totals;        // [column][8], may be null
+    uint32_t ntiles;
+    uint32_t single;         // n <= one tile: step 3 alone, seeded by init, writes the totals
+};
+struct ExtAccumSeeds { uint32_t v[EXT_ACCUM_INLINE_COLUMNS][4]; };   // init[b]: plain for sums, Montgomery forms for products
+TOYNI_HD uint32_t* ext_accum_tile_aggregates(const ExtAccumArgs& a, uint32_t col) { return a.tiles + (uint64_t)col * EXT_ACCUM_TILE_WORDS * a.ntiles; }
+TOYNI_HD uint32_t* ext_accum_tile_zeros(const ExtAccumArgs& a, uint32_t col) { return ext_accum_tile_aggregates(a, col) + 4ull * a.ntiles; }
+
+template <int OP> TOYNI_HD Ext4 ext_accum_identity() { return Ext4{{OP == (int)SCAN_PRODUCT ? BB_R1 : 0u, 0u, 0u, 0u}}; }
+// a * b, all three in Montgomery form: b becomes the prepared right factor of ext_mul (its multiples of 11 through X^4 = EXT_W_R)
+TOYNI_HD Ext4 ext_mul_general(const Ext4& a, const Ext4& b) {
+    ExtFactor f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        f.b[k] = b.c[k];
+        f.b11[k] = k ? mont_mul(b.c[k], EXT_W_R) : 0u;   // ext_mul never reads b11[0]
+    }
+    return ext_mul(a, f);
+}
+template <int OP> TOYNI_HD Ext4 ext_accum_combine(const Ext4& a, const Ext4& b) {
+    if (OP == (int)SCAN_PRODUCT) return ext_mul_general(a, b);
+    Ext4 r;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r.c[k] = bb_add(a.c[k], b.c[k]);
+    return r;
+}
+template <int OP> TOYNI_HD Ext4 ext_accum_to_plain(const Ext4& v) {
+    if (OP != (int)SCAN_PRODUCT) return v;
+    return Ext4{{from_mont(v.c[0]), from_mont(v.c[1]), from_mont(v.c[2]), from_mont(v.c[3])}};
+}
+// the G elements of an Ext column from i0 on (coordinate columns `stride` apart), each coordinate column as scan_group_load reads it
+template <int G>
+TOYNI_HD void ext_column_group_load(const uint32_t* col0, uint64_t stride, uint64_t i0, uint64_t n, Ext4 (&v)[G]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint32_t w[G];
+        scan_group_load<G>(col0 + (uint64_t)k * stride, i0, n, 0u, w);
+#pragma unroll
+        for (int j = 0; j < G; ++j) v[j].c[k] = w[j];
+    }
+}
+template <int G>
+TOYNI_HD void ext_column_group_store(uint32_t* col0, uint64_t stride, uint64_t i0, uint64_t n, const Ext4 (&v)[G]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        uint32_t w[G];
+#pragma unroll
+        for (int j = 0; j < G; ++j) w[j] = v[j].c[k];
+        scan_group_store<G>(col0 + (uint64_t)k * stride, i0, n, w);
+    }
+}
+// the G elements of column `col` of an operand from i0 on, plain, the shift added; past n: the shift (width 4, 1) -- never used
+template <int G>
+TOYNI_HD void ext_accum_operand_load(const ExtAccumOperand& o, uint32_t col, uint64_t i0, uint64_t n, Ext4 (&v)[G]) {
+    if (o.width == 4u) {
+        ext_column_group_load<G>(o.values + 4ull * col * o.stride, o.stride, i0, n, v);
+#pragma unroll
+        for (int j = 0; j < G; ++j)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[j].c[k] = bb_add(v[j].c[k], o.shift[k]);
+    } else if (o.width == 1u) {
+        uint32_t w[G];
+        scan_group_load<G>(o.values + (uint64_t)col * o.stride, i0, n, 0u, w);
+#pragma unroll
+        for (int j = 0; j < G; ++j) v[j] = Ext4{{bb_add(w[j], o.shift[0]), o.shift[1], o.shift[2], o.shift[3]}};
+    } else {
+#pragma unroll
+        for (int j = 0; j < G; ++j) v[j] = Ext4{{1u, 0u, 0u, 0u}};
+    }
+}
+// invR[j] = a_j^-1 in Montgomery form (0 for a_j = 0) for G PLAIN Ext elements behind ONE base inversion, through the tower
+// F_p < F_p[Y]/(Y^2 - 11) < Ext, Y = X^2:  a = A0 + A1 X with A0 = a0 + a2 Y, A1 = a1 + a3 Y;  B = A0^2 - Y A1^2 = B0 + B1 Y;
+// N = B0^2 - 11 B1^2 in F_p;  a^-1 = (A0 - A1 X)(B0 - B1 Y) / N.  N = 0 only for a = 0 (two norms of field extensions).  The G norms
+// share the inversion by Montgomery's trick, a zero norm kept out of the chain with the marker of deep_point_inverses.
+// The plain coordinates are read as Montgomery forms of a / R, as scan_group_inverses reads its residues: every step is then a
+// Montgomery-domain step for a / R, whose inverse a^-1 R in Montgomery form is a^-1 R^2; the one from_mont of the inverted product
+// takes that R back out of all G results.
+template <int G>
+TOYNI_HD void ext_tower_inverses(const Ext4 (&a)[G], uint32_t (&invR)[G][4]) {
+    uint32_t b0[G], b1[G], dR[G], pre[G];
+    uint32_t acc = BB_R1;
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+        const uint32_t a2w = mont_mul(a[j].c[2], EXT_W_R), a3w = mont_mul(a[j].c[3], EXT_W_R);   // 11 a2, 11 a3
+        const uint32_t t13 = mont_mul(a[j].c[1], a3w), t02 = mont_mul(a[j].c[0], a[j].c[2]);
+        b0[j] = bb_sub(mont_dot2(a[j].c[0], a[j].c[0], a[j].c[2], a2w), bb_add(t13, t13));       // a0^2 + 11 a2^2 - 22 a1 a3
+        b1[j] = bb_sub(bb_add(t02, t02), mont_dot2(a[j].c[1], a[j].c[1], a[j].c[3], a3w));       // 2 a0 a2 - a1^2 - 11 a3^2
+        dR[j] = bb_sub(mont_mul(b0[j], b0[j]), mont_mul(mont_mul(b1[j], b1[j]), EXT_W_R));       // N
+        if (dR[j] == 0u) dR[j] = BB_R1 | 0x80000000u;                                            // marker (never a canonical value)
+        pre[j] = acc;
+        acc = mont_mul(acc, (dR[j] & 0x80000000u) ? BB_R1 : dR[j]);
+    }
+    uint32_t inv = from_mont(mont_inv(acc));
+#pragma unroll
+    for (int j = G - 1; j >= 0; --j) {
+        const bool zero = (dR[j] & 0x80000000u) != 0u;
+        const uint32_t ni = zero ? 0u : mont_mul(inv, pre[j]);
+        if (!zero) inv = mont_mul(inv, dR[j]);
+        const uint32_t c0 = mont_mul(b0[j], ni), c1 = mont_mul(bb_sub(0u, b1[j]), ni);           // (B0 - B1 Y) / N
+        const uint32_t c1w = mont_mul(c1, EXT_W_R);
+        invR[j][0] = mont_dot2(a[j].c[0], c0, a[j].c[2], c1w);                                 // A0 C
+        invR[j][2] = mont_dot2(a[j].c[0], c1, a[j].c[2], c0);
+        invR[j][1] = bb_sub(0u, mont_dot2(a[j].c[1], c0, a[j].c[3], c1w));                     // -A1 C
+        invR[j][3] = bb_sub(0u, mont_dot2(a[j].c[1], c1, a[j].c[3], c0));
+    }
+}
+TOYNI_HD uint32_t ext_is_zero(const Ext4& v) { return (v.c[0] | v.c[1] | v.c[2] | v.c[3]) == 0u ? 1u : 0u; }
+// the inverses of column `col`'s G denominators from i0 on, in Montgomery form (0 for a zero denominator); returns the zeros below n.
+// An inverse is zero only where the denominator is (a field), so the zeros are read off the results.
+template <int G>
+TOYNI_HD uint32_t ext_accum_group_inverses(const ExtAccumArgs& a, uint32_t col, uint64_t i0, uint64_t n, Ext4 (&invR)[G]) {
+    uint32_t r[G][4];   // both forms write the one array
+    if (a.den.width == 1u) {   // gamma + v_i for a base column: the norm form of 3h with the column's values as points
+        uint32_t xR[G];
+        scan_group_load<G>(a.den.values + (uint64_t)col * a.den.stride, i0, n, 0u, xR);
+#pragma unroll
+        for (int j = 0; j < G; ++j) xR[j] = to_mont(xR[j]);
+        ext_shifted_inverses<G>(a.den_inv, xR, r);
+    } else {
+        Ext4 d[G];
+        ext_accum_operand_load<G>(a.den, col, i0, n, d);
+        ext_tower_inverses<G>(d, r);
+    }
+    uint32_t zeros = 0;
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+        invR[j] = Ext4{{r[j][0], r[j][1], r[j][2], r[j][3]}};
+        zeros += i0 + (uint64_t)j < n ? ext_is_zero(invR[j]) : 0u;
+    }
+    return zeros;
+}
+// the G terms num / den of column `col` from i0 on in the form the op scans (plain for a sum, Montgomery forms for a product); the
+// identity past n.  Returns the zero denominators met below n.
+template <int OP, int G>
+TOYNI_HD uint32_t ext_accum_group_terms(const ExtAccumArgs& a, uint32_t col, uint64_t i0, uint64_t n, Ext4 (&t)[G]) {
+    constexpr bool PROD = OP == (int)SCAN_PRODUCT;
+    uint32_t zeros = 0;
+    if (a.den.width != 0u) {
+        Ext4 invR[G];
+        zeros = ext_accum_group_inverses<G>(a, col, i0, n, invR);
+        if (a.num.width != 0u) {
+            ext_accum_operand_load<G>(a.num, col, i0, n, t);
+#pragma unroll
+            for (int j = 0; j < G; ++j) {
+                if (PROD) t[j] = Ext4{{to_mont(t[j].c[0]), to_mont(t[j].c[1]), to_mont(t[j].c[2]), to_mont(t[j].c[3])}};
+                t[j] = ext_mul_general(t[j], invR[j]);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < G; ++j) t[j] = PROD ? invR[j] : Ext4{{from_mont(invR[j].c[0]), from_mont(invR[j].c[1]), from_mont(invR[j].c[2]), from_mont(invR[j].c[3])}};
+        }
+    } else {
+        ext_accum_operand_load<G>(a.num, col, i0, n, t);
+        if (PROD) {
+#pragma unroll
+            for (int j = 0; j < G; ++j) t[j] = Ext4{{to_mont(t[j].c[0]), to_mont(t[j].c[1]), to_mont(t[j].c[2]), to_mont(t[j].c[3])}};
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < G; ++j)
+        if (i0 + (uint64_t)j >= n) t[j] = ext_accum_identity<OP>();
+    return zeros;
+}
+// thread-serial part: ex[j] = t[0] o ... o t[j-1]; returns the group's total
+template <int OP, int G>
+TOYNI_HD Ext4 ext_accum_thread_serial(const Ext4 (&t)[G], Ext4 (&ex)[G]) {
+    Ext4 acc = ext_accum_identity<OP>();
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+        ex[j] = acc;
+        acc = ext_accum_combine<OP>(acc, t[j]);
+    }
+    return acc;
+}
+// from the waves' totals (LDS, 16 bytes per wave): what the waves below `wave` combine to; `total` = all of them
+template <int OP, int NW>
+TOYNI_HD Ext4 ext_accum_waves_below(const Ext4* wave_tot, uint32_t wave, Ext4& total) {
+    Ext4 pre = ext_accum_identity<OP>();
+    total = ext_accum_identity<OP>();
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        if ((uint32_t)w == wave) pre = total;
+        total = ext_accum_combine<OP>(total, wave_tot[w]);
+    }
+    return pre;
+}
+// what step 3 stores: base o ex[j], as plain residues
+template <int OP, int G>
+TOYNI_HD void ext_accum_group_finish(const Ext4& base, const Ext4 (&ex)[G], Ext4 (&o)[G]) {
+#pragma unroll
+    for (int j = 0; j < G; ++j) o[j] = ext_accum_to_plain<OP>(ext_accum_combine<OP>(base, ex[j]));
+}
+// out_j = in_j^-1 (0 for 0), plain in and out, for the G elements of one Ext column from i0 on; returns the zeros below `count`
+template <int G>
+TOYNI_HD uint32_t ext_invert_group(const uint32_t* in, uint64_t in_stride, uint32_t* out, uint64_t out_stride, uint64_t i0, uint64_t count) {
+    Ext4 v[G];
+    uint32_t invR[G][4];
+    ext_column_group_load<G>(in, in_stride, i0, count, v);
+    ext_tower_inverses<G>(v, invR);
+    uint32_t zeros = 0;
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+        v[j] = Ext4{{from_mont(invR[j][0]), from_mont(invR[j][1]), from_mont(invR[j][2]), from_mont(invR[j][3])}};
+        zeros += i0 + (uint64_t)j < count ? ext_is_zero(v[j]) : 0u;
+    }
+    ext_column_group_store<G>(out, out_stride, i0, count, v);
+    return zeros;
+}
+
 // ---- polynomial evaluation at up to POLY_MAX_POINTS points ----
 constexpr int POLY_MAX_POINTS = 4;
 constexpr uint32_t POLY_PER_THREAD = 16, POLY_THREADS = 256, POLY_CHUNK = POLY_PER_THREAD * POLY_THREADS;

@@ -1004,6 +1004,132 @@ __global__ void __launch_bounds__(SCAN_THREADS) batch_inverse_kernel(const uint3
     }
 }
 
+// Accumulator columns under an Ext challenge (prover_kernels.hpp, include/toyni_hip.h 3i): the three launches above with Ext values.
+// Every workgroup is EXT_ACCUM_THREADS threads, every thread owns EXT_ACCUM_GROUP consecutive elements; the cross-lane step moves the
+// four words of a value, the waves' totals go through 16 bytes of LDS per wave.  Every thread of the workgroup reaches both barriers.
+template <int OP>
+__device__ __forceinline__ Ext4 ext_accum_wave_inclusive(Ext4 v, uint32_t lane) {
+#pragma unroll
+    for (uint32_t delta = 1; delta < SCAN_WAVE; delta <<= 1) {
+        Ext4 below;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) below.c[k] = scan_lane_up(v.c[k], delta);
+        if (lane >= delta) v = ext_accum_combine<OP>(below, v);
+    }
+    return v;
+}
+// what the threads below this one combine to, and in `total` the whole workgroup's; wave_tot: EXT_ACCUM_THREADS / 64 values of LDS
+template <int OP>
+__device__ __forceinline__ Ext4 ext_accum_block_exclusive(const Ext4& v, Ext4* wave_tot, Ext4& total) {
+    constexpr int NW = EXT_ACCUM_THREADS / SCAN_WAVE;
+    const uint32_t lane = threadIdx.x & (SCAN_WAVE - 1), wave = threadIdx.x / SCAN_WAVE;
+    const Ext4 inc = ext_accum_wave_inclusive<OP>(v, lane);
+    if (lane == SCAN_WAVE - 1) wave_tot[wave] = inc;
+    __syncthreads();
+    Ext4 up;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) up.c[k] = scan_lane_up(inc.c[k], 1);
+    const Ext4 pre = ext_accum_waves_below<OP, NW>(wave_tot, wave, total);
+    __syncthreads();   // wave_tot may be written again
+    return lane ? ext_accum_combine<OP>(pre, up) : pre;
+}
+static_assert(EXT_ACCUM_THREADS == SCAN_THREADS, "the zero counts go through scan_block_exclusive<SCAN_COUNT>");
+// step 1, grid (tile, column): one aggregate and one zero count per tile
+template <int OP>
+__global__ void __launch_bounds__(EXT_ACCUM_THREADS) ext_accum_aggregate_kernel(const ExtAccumArgs a) {
+    __shared__ Ext4 wave_tot[EXT_ACCUM_THREADS / SCAN_WAVE];
+    __shared__ uint32_t wave_zeros[EXT_ACCUM_THREADS / SCAN_WAVE];
+    const uint32_t col = blockIdx.y, tile = blockIdx.x;
+    const uint64_t i0 = (uint64_t)tile * EXT_ACCUM_TILE + (uint64_t)threadIdx.x * EXT_ACCUM_GROUP;
+    Ext4 t[EXT_ACCUM_GROUP], ex[EXT_ACCUM_GROUP], total;
+    uint32_t ztotal;
+    const uint32_t zeros = ext_accum_group_terms<OP, EXT_ACCUM_GROUP>(a, col, i0, a.n, t);
+    (void)ext_accum_block_exclusive<OP>(ext_accum_thread_serial<OP, EXT_ACCUM_GROUP>(t, ex), wave_tot, total);
+    (void)scan_block_exclusive<SCAN_COUNT>(zeros, wave_zeros, ztotal);
+    if (threadIdx.x == 0) {
+        uint32_t* agg = ext_accum_tile_aggregates(a, col);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) agg[(uint64_t)k * a.ntiles + tile] = total.c[k];
+        ext_accum_tile_zeros(a, col)[tile] = ztotal;
+    }
+}
+// step 2, one workgroup per column: the exclusive scan of the column's aggregates, seeded with init, in rounds of EXT_ACCUM_TILE; the totals
+template <int OP>
+__global__ void __launch_bounds__(EXT_ACCUM_THREADS) ext_accum_prefix_kernel(const ExtAccumArgs a, const ExtAccumSeeds in) {
+    __shared__ Ext4 wave_tot[EXT_ACCUM_THREADS / SCAN_WAVE];
+    __shared__ uint32_t wave_zeros[EXT_ACCUM_THREADS / SCAN_WAVE];
+    const uint32_t col = blockIdx.x;
+    uint32_t* agg = ext_accum_tile_aggregates(a, col);
+    Ext4 carry = {{in.v[col][0], in.v[col][1], in.v[col][2], in.v[col][3]}};
+    for (uint32_t base = 0; base < a.ntiles; base += EXT_ACCUM_TILE) {
+        const uint64_t i0 = (uint64_t)base + threadIdx.x * EXT_ACCUM_GROUP;
+        Ext4 t[EXT_ACCUM_GROUP], ex[EXT_ACCUM_GROUP], total;
+        ext_column_group_load<EXT_ACCUM_GROUP>(agg, a.ntiles, i0, a.ntiles, t);
+#pragma unroll
+        for (int j = 0; j < (int)EXT_ACCUM_GROUP; ++j)
+            if (i0 + (uint64_t)j >= a.ntiles) t[j] = ext_accum_identity<OP>();
+        const Ext4 pre = ext_accum_block_exclusive<OP>(ext_accum_thread_serial<OP, EXT_ACCUM_GROUP>(t, ex), wave_tot, total);
+        const Ext4 mine = ext_accum_combine<OP>(carry, pre);
+#pragma unroll
+        for (int j = 0; j < (int)EXT_ACCUM_GROUP; ++j) t[j] = ext_accum_combine<OP>(mine, ex[j]);
+        ext_column_group_store<EXT_ACCUM_GROUP>(agg, a.ntiles, i0, a.ntiles, t);
+        carry = ext_accum_combine<OP>(carry, total);
+    }
+    const uint32_t* zc = ext_accum_tile_zeros(a, col);
+    uint32_t zeros = 0, ztotal;
+    for (uint32_t k = threadIdx.x; k < a.ntiles; k += EXT_ACCUM_THREADS) zeros += zc[k];
+    (void)scan_block_exclusive<SCAN_COUNT>(zeros, wave_zeros, ztotal);
+    if (threadIdx.x == 0 && a.totals) {
+        const Ext4 tot = ext_accum_to_plain<OP>(carry);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) a.totals[8 * col + k] = tot.c[k];
+        a.totals[8 * col + 4] = ztotal;
+#pragma unroll
+        for (int k = 5; k < 8; ++k) a.totals[8 * col + k] = 0u;
+    }
+}
+// step 3, grid (tile, column): the terms again, the scan inside the tile on top of the tile's prefix.  With a.single the grid is the
+// columns alone (n <= one tile): the prefix is init and the totals are written here.  In place on a width-4 operand: a thread has read
+// all it needs of its own elements before it stores them, and no thread reads another's.
+template <int OP>
+__global__ void __launch_bounds__(EXT_ACCUM_THREADS) ext_accum_apply_kernel(const ExtAccumArgs a, const ExtAccumSeeds in) {
+    __shared__ Ext4 wave_tot[EXT_ACCUM_THREADS / SCAN_WAVE];
+    __shared__ uint32_t wave_zeros[EXT_ACCUM_THREADS / SCAN_WAVE];
+    const uint32_t col = blockIdx.y, tile = blockIdx.x;
+    const uint64_t i0 = (uint64_t)tile * EXT_ACCUM_TILE + (uint64_t)threadIdx.x * EXT_ACCUM_GROUP;
+    Ext4 t[EXT_ACCUM_GROUP], ex[EXT_ACCUM_GROUP], total, seed;
+    const uint32_t zeros = ext_accum_group_terms<OP, EXT_ACCUM_GROUP>(a, col, i0, a.n, t);
+    const Ext4 pre = ext_accum_block_exclusive<OP>(ext_accum_thread_serial<OP, EXT_ACCUM_GROUP>(t, ex), wave_tot, total);
+    const uint32_t* agg = ext_accum_tile_aggregates(a, col);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) seed.c[k] = a.single ? in.v[col][k] : TOYNI_UNIFORM(agg[(uint64_t)k * a.ntiles + tile]);
+    ext_accum_group_finish<OP, EXT_ACCUM_GROUP>(ext_accum_combine<OP>(seed, pre), ex, t);
+    ext_column_group_store<EXT_ACCUM_GROUP>(a.out + 4ull * col * a.out_stride, a.out_stride, i0, a.n, t);
+    if (a.single) {
+        uint32_t ztotal;
+        (void)scan_block_exclusive<SCAN_COUNT>(zeros, wave_zeros, ztotal);
+        if (threadIdx.x == 0 && a.totals) {
+            const Ext4 tot = ext_accum_to_plain<OP>(ext_accum_combine<OP>(seed, total));
+#pragma unroll
+            for (int k = 0; k < 4; ++k) a.totals[8 * col + k] = tot.c[k];
+            a.totals[8 * col + 4] = ztotal;
+#pragma unroll
+            for (int k = 5; k < 8; ++k) a.totals[8 * col + k] = 0u;
+        }
+    }
+}
+// out[i] = in[i]^-1 (0 for 0) on one Ext column: the tower inversion alone.  zero_count (may be null) was cleared ahead of the launch.
+__global__ void __launch_bounds__(EXT_ACCUM_THREADS) ext_invert_columns_kernel(const uint32_t* in, uint64_t in_stride, uint32_t* out,
+                                                                               uint64_t out_stride, uint64_t count, uint32_t* zero_count) {
+    const uint64_t i0 = ((uint64_t)blockIdx.x * EXT_ACCUM_THREADS + threadIdx.x) * EXT_ACCUM_GROUP;
+    const uint32_t zeros = ext_invert_group<EXT_ACCUM_GROUP>(in, in_stride, out, out_stride, i0, count);
+    if (zero_count) {
+        const uint32_t lane = threadIdx.x & (SCAN_WAVE - 1);
+        const uint32_t wave_zeros = scan_wave_inclusive<SCAN_COUNT>(zeros, lane);
+        if (lane == SCAN_WAVE - 1 && wave_zeros) atomicAdd(zero_count, wave_zeros);
+    }
+}
+
 // Merkle openings: one thread per (opening, level) copies the sibling digest; one thread per opening adds salt, value, flags
 struct OpenGroup {
     const Digest* levels;
@@ -1953,6 +2079,17 @@ void column_scan_launch(const ScanArgs& a, const ScanInit& in, unsigned cols, hi
     hipLaunchKernelGGL(column_scan_aggregate_kernel<OP>, dim3(a.ntiles, cols), dim3(SCAN_THREADS), 0, s, a);
     hipLaunchKernelGGL(column_scan_prefix_kernel<OP>, dim3(cols), dim3(SCAN_THREADS), 0, s, a, in);
     hipLaunchKernelGGL(column_scan_apply_kernel<OP>, dim3(a.ntiles, cols), dim3(SCAN_THREADS), 0, s, a, in);
+}
+// the launch sequence of toyni_column_scan_ext_device for up to EXT_ACCUM_INLINE_COLUMNS Ext columns
+template <int OP>
+void ext_accum_launch(const ExtAccumArgs& a, const ExtAccumSeeds& in, unsigned cols, hipStream_t s) {
+    if (a.single) {
+        hipLaunchKernelGGL(ext_accum_apply_kernel<OP>, dim3(1, cols), dim3(EXT_ACCUM_THREADS), 0, s, a, in);
+        return;
+    }
+    hipLaunchKernelGGL(ext_accum_aggregate_kernel<OP>, dim3(a.ntiles, cols), dim3(EXT_ACCUM_THREADS), 0, s, a);
+    hipLaunchKernelGGL(ext_accum_prefix_kernel<OP>, dim3(cols), dim3(EXT_ACCUM_THREADS), 0, s, a, in);
+    hipLaunchKernelGGL(ext_accum_apply_kernel<OP>, dim3(a.ntiles, cols), dim3(EXT_ACCUM_THREADS), 0, s, a, in);
 }
 
 bool is_pow2(size_t v) { return v && !(v & (v - 1)); }
@@ -3392,6 +3529,89 @@ int toyni_column_scan_device(toyni_ntt_ctx* c, const uint32_t* d_num, size_t num
         a.totals = d_totals ? d_totals + 2 * b0 : nullptr;
         if (op == TOYNI_SCAN_PRODUCT) column_scan_launch<SCAN_PRODUCT>(a, in, cols, s);
         else column_scan_launch<SCAN_SUM>(a, in, cols, s);
+    }
+    return (int)hipGetLastError();
+}
+
+// ---- section 3i: accumulator columns under an Ext challenge ----
+size_t toyni_column_scan_ext_tile(void) { return EXT_ACCUM_TILE; }
+
+int toyni_batch_inverse_ext_device(const uint32_t* d_in, size_t in_stride, uint32_t* d_out, size_t out_stride, size_t count,
+                                   uint32_t* d_zero_count, void* stream) {
+    if (!d_in || !d_out) return TOYNI_E_NULL;
+    if (count > ((size_t)1 << 32) || in_stride < count || out_stride < count ||
+        (((uintptr_t)d_in | (uintptr_t)d_out | (uintptr_t)d_zero_count) & 3))
+        return TOYNI_E_RANGE;
+    hipStream_t s = (hipStream_t)stream;
+    if (d_zero_count) HIPCHK(hipMemsetAsync(d_zero_count, 0, sizeof(uint32_t), s));
+    if (count == 0) return TOYNI_OK;
+    hipLaunchKernelGGL(ext_invert_columns_kernel, dim3((unsigned)((count + EXT_ACCUM_TILE - 1) / EXT_ACCUM_TILE)), dim3(EXT_ACCUM_THREADS), 0, s,
+                       d_in, (uint64_t)in_stride, d_out, (uint64_t)out_stride, (uint64_t)count, d_zero_count);
+    return (int)hipGetLastError();
+}
+
+namespace {
+// an operand as the header reads it: width 0 or a null pointer is the constant 1.  false: refused.
+bool ext_operand_ok(const toyni_ext_operand* o, size_t n, size_t batch, ExtAccumOperand* out) {
+    *out = ExtAccumOperand{};
+    if (!o || o->width == 0) return true;
+    if ((o->width != 1 && o->width != 4) || !o->d_values || ((uintptr_t)o->d_values & 3)) return false;
+    if ((o->width == 4 || batch > 1) && o->stride < n) return false;
+    for (int k = 0; k < 4; ++k)
+        if (o->shift[k] >= BB_P) return false;
+    out->values = o->d_values;
+    out->stride = o->stride;
+    out->width = o->width;
+    for (int k = 0; k < 4; ++k) out->shift[k] = o->shift[k];
+    return true;
+}
+}  // namespace
+
+int toyni_column_scan_ext_device(toyni_ntt_ctx* c, const toyni_ext_operand* num, const toyni_ext_operand* den, uint32_t* d_out, size_t out_stride,
+                                 size_t n, size_t batch, int op, const uint32_t* init, uint32_t* d_totals, void* stream) {
+    // every refusal is decided on the arguments alone: the context is not touched before they have passed
+    if (!c || !d_out || !init) return TOYNI_E_NULL;
+    ExtAccumArgs a{};
+    if (!ext_operand_ok(num, n, batch, &a.num) || !ext_operand_ok(den, n, batch, &a.den) || (a.num.width == 0 && a.den.width == 0)) return TOYNI_E_RANGE;
+    if ((op != TOYNI_SCAN_SUM && op != TOYNI_SCAN_PRODUCT) || n > ((size_t)1 << SCAN_MAX_LOG_N) || batch >= ((size_t)1 << 14) || out_stride < n ||
+        (((uintptr_t)d_out | (uintptr_t)d_totals) & 3))
+        return TOYNI_E_RANGE;
+    for (size_t w = 0; w < 4 * batch; ++w)
+        if (init[w] >= BB_P) return TOYNI_E_RANGE;
+    if (batch == 0 || n == 0) return TOYNI_OK;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (a.den.width == 1) {   // 1 / (shift + v) = 1 / (v - z) with z = -shift: adj_z and m_z, expanded once per call
+        uint32_t z[4];
+        for (int k = 0; k < 4; ++k) z[k] = a.den.shift[k] ? BB_P - a.den.shift[k] : 0u;
+        a.den_inv = ext_shift_host(z);
+    }
+    a.out_stride = out_stride;
+    a.n = n;
+    a.ntiles = (uint32_t)((n + EXT_ACCUM_TILE - 1) / EXT_ACCUM_TILE);
+    a.single = a.ntiles == 1 ? 1u : 0u;
+    if (!a.single) {   // the aggregates and zero counts of one launch sequence's columns; a warm context finds the buffer in place
+        toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+        int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words,
+                      (size_t)EXT_ACCUM_TILE_WORDS * a.ntiles * std::min<size_t>(batch, EXT_ACCUM_INLINE_COLUMNS), sizeof(uint32_t));
+        if (rc) return rc;
+        a.tiles = sc.d_lde32;
+    }
+    // the seeds ride in the kernel arguments, EXT_ACCUM_INLINE_COLUMNS columns to a launch sequence (the stream orders the sequences,
+    // so they share the buffer)
+    const ExtAccumOperand num0 = a.num, den0 = a.den;
+    for (size_t b0 = 0; b0 < batch; b0 += EXT_ACCUM_INLINE_COLUMNS) {
+        const unsigned cols = (unsigned)std::min<size_t>(batch - b0, EXT_ACCUM_INLINE_COLUMNS);
+        ExtAccumSeeds in{};
+        for (unsigned b = 0; b < cols; ++b)
+            for (int k = 0; k < 4; ++k) in.v[b][k] = op == TOYNI_SCAN_PRODUCT ? to_mont_host(init[4 * (b0 + b) + k]) : init[4 * (b0 + b) + k];
+        a.num.values = num0.values ? num0.values + b0 * num0.width * num0.stride : nullptr;
+        a.den.values = den0.values ? den0.values + b0 * den0.width * den0.stride : nullptr;
+        a.out = d_out + 4 * b0 * out_stride;
+        a.totals = d_totals ? d_totals + 8 * b0 : nullptr;
+        if (op == TOYNI_SCAN_PRODUCT) ext_accum_launch<SCAN_PRODUCT>(a, in, cols, s);
+        else ext_accum_launch<SCAN_SUM>(a, in, cols, s);
     }
     return (int)hipGetLastError();
 }

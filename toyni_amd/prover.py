@@ -197,6 +197,8 @@ class AirExpr:
         self.builder, self.key = builder, key
 
     def _bin(self, op, other, swap=False):
+        if isinstance(other, AirExt):      # base o Ext: the Ext operand's reflected method answers
+            return NotImplemented
         o = other if isinstance(other, AirExpr) else self.builder.const(other)
         return self.builder._node((op, o, self) if swap else (op, self, o))
 
@@ -283,6 +285,79 @@ class AirBuilder:
                 free.append(dst)
         return insns
 
+    # Ext = F_p[X]/(X^4 - 11) on top of the base-field expressions (include/toyni_hip.h 3i): an Ext expression is an AirExt of four
+    # AirExpr, one per coordinate, so the constraints that tie an Ext accumulator (four base columns) to the trace compile to
+    # ordinary base-field programs.  Nothing above changes: a program that uses none of this compiles as before.
+    def ext_cell(self, matrix, first_column, rotation=0):
+        """The Ext column held in columns first_column .. first_column + 3 of `matrix`."""
+        return AirExt(tuple(self.cell(matrix, int(first_column) + k, rotation) for k in range(4)))
+
+    def ext_const(self, v4):
+        v = [int(c) for c in v4]
+        assert len(v) == 4
+        return AirExt(tuple(self.const(c) for c in v))
+
+    def ext(self, e):
+        """An Ext expression from an AirExt (itself), a base-field AirExpr or an int (embedded in coordinate 0)."""
+        if isinstance(e, AirExt):
+            return e
+        zero = self.const(0)
+        return AirExt((e if isinstance(e, AirExpr) else self.const(e), zero, zero, zero))
+
+    def emit_ext(self, k, e, divide=True):
+        """The Ext constraint number k: base constraints 4 k .. 4 k + 3, one per coordinate (an Ext weight's four coordinates, each
+        in its own call, weigh them)."""
+        e = self.ext(e)
+        for j in range(4):
+            self.emit(4 * int(k) + j, e.c[j], divide)
+
+
+EXT_W = 11   # X^4 = EXT_W
+
+
+class AirExt:
+    """An Ext-valued expression: four AirExpr coordinates; + - * with AirExt, AirExpr (base field) and ints."""
+
+    def __init__(self, c):
+        assert len(c) == 4
+        self.c = tuple(c)
+
+    def _other(self, o):
+        return self.c[0].builder.ext(o)
+
+    def __add__(self, o):
+        o = self._other(o)
+        return AirExt(tuple(a + b for a, b in zip(self.c, o.c)))
+
+    __radd__ = __add__
+
+    def __sub__(self, o):
+        o = self._other(o)
+        return AirExt(tuple(a - b for a, b in zip(self.c, o.c)))
+
+    def __rsub__(self, o):
+        return self._other(o) - self
+
+    def __mul__(self, o):
+        if not isinstance(o, AirExt):      # a base-field factor scales every coordinate
+            return AirExt(tuple(a * o for a in self.c))
+        out = []
+        for k in range(4):                 # schoolbook, the high half folded back through X^4 = 11
+            lo = [self.c[i] * o.c[k - i] for i in range(k + 1)]
+            hi = [self.c[i] * o.c[k + 4 - i] for i in range(k + 1, 4)]
+            acc = lo[0]
+            for t in lo[1:]:
+                acc = acc + t
+            if hi:
+                h = hi[0]
+                for t in hi[1:]:
+                    h = h + t
+                acc = acc + h * EXT_W
+            out.append(acc)
+        return AirExt(tuple(out))
+
+    __rmul__ = __mul__
+
 
 # ---- accumulator columns (include/toyni_hip.h 3g) ----
 SCAN_SUM, SCAN_PRODUCT = 0, 1
@@ -311,6 +386,45 @@ def column_scan_device(ctx, num: int, den: int, out: int, n: int, batch: int = 1
     ns, ds, os_ = strides if strides is not None else (n, n, n)
     check(lib.toyni_column_scan_device(ctx.handle, num or None, ns, den or None, ds, out, os_, n, batch, op, i.ctypes.data, totals or None,
                                        stream or None), "GPU column scan failed")
+
+
+# ---- accumulator columns under an Ext challenge (include/toyni_hip.h 3i) ----
+class _ExtOperand(ctypes.Structure):   # toyni_ext_operand
+    _fields_ = [("d_values", ctypes.c_void_p), ("stride", ctypes.c_size_t), ("width", ctypes.c_uint32), ("shift", ctypes.c_uint32 * 4)]
+
+
+def ExtOperand(d_values: int = 0, stride: int = 0, width: int = 0, shift=(0, 0, 0, 0)) -> _ExtOperand:
+    """An operand of column_scan_ext_device.  width 4: an Ext column (four base columns `stride` words apart) per accumulator; width 1:
+    a base column embedded in Ext; width 0: the constant 1.  shift (four coordinates) is added to every element: gamma + v_i."""
+    sh = [int(c) for c in shift]
+    assert len(sh) == 4
+    return _ExtOperand(d_values or None, stride, width, (ctypes.c_uint32 * 4)(*sh))
+
+
+def column_scan_ext_tile() -> int:
+    """Ext elements one workgroup owns: a column of at most this many takes a single launch."""
+    return lib.toyni_column_scan_ext_tile()
+
+
+def batch_inverse_ext_device(d_in: int, in_stride: int, d_out: int, out_stride: int, count: int, d_zero_count: int = 0, stream=None) -> None:
+    """out_i = in_i^-1 in Ext, 0 for 0, on one Ext column (four base columns a stride apart); d_zero_count (one device word, optional)
+    receives the number of zeros.  d_out may be d_in with equal strides."""
+    check(lib.toyni_batch_inverse_ext_device(d_in, in_stride, d_out, out_stride, count, d_zero_count or None, stream or None),
+          "GPU Ext batch inversion failed")
+
+
+def column_scan_ext_device(ctx, num, den, out: int, out_stride: int, n: int, batch: int = 1, op: int = SCAN_SUM, init=None, totals: int = 0,
+                           stream=None) -> None:
+    """out[0] = init[b], out[i] = out[i-1] (+ or *) num[i-1] / den[i-1] in Ext for each of `batch` Ext columns (include/toyni_hip.h 3i).
+    num, den: ExtOperand or None (the constant 1); a zero denominator makes the term 0.  out: 4 * batch base columns out_stride words
+    apart.  init: batch x 4 residues (default: the op's identity).  totals: 8 * batch device words, optional: per column the
+    wrap-around value (4), the zero denominators (1) and three zero words."""
+    if init is None:
+        init = [[1 if op == SCAN_PRODUCT else 0, 0, 0, 0]] * batch
+    i = np.ascontiguousarray(init, dtype=np.uint32)
+    assert i.size == 4 * batch
+    check(lib.toyni_column_scan_ext_device(ctx.handle, ctypes.byref(num) if num is not None else None, ctypes.byref(den) if den is not None else None,
+                                           out, out_stride, n, batch, op, i.ctypes.data, totals or None, stream or None), "GPU Ext column scan failed")
 
 
 def merkle_open_record_bytes(n: int) -> int:
