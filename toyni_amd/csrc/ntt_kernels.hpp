@@ -80,6 +80,10 @@ struct PassArgs {
     uint32_t in_split_shift, in_split_extra;
     uint32_t out_split_shift, out_split_extra, out_prefix_log;
     uint32_t row0;
+    // KIND_COL, set by the launcher from seeds_launch_invariant (ntt_route.hpp): every workgroup of this launch stays on one column
+    // tile, so the prefetching kernels look the twiddle seeds (and the forward coset seed) up once, ahead of the tile loop.  0: per
+    // tile, as the tile-by-tile steppers (phase1 / phase2) always do.
+    uint32_t seeds_invariant;
 };
 
 // Diagnostic builds only (-DTOYNI_ABLATE=1|2|3, never the shipped library): bit 0 replaces tile loads by register
@@ -772,11 +776,18 @@ struct Pass {
         }
         return r;
     }
+    // the seed itself, s^j0: split from the scaling so that the persistent kernel can keep it across tiles (it depends on the tile
+    // through its column index alone)
+    static TOYNI_HD uint32_t in_seed_finish(const PassArgs& a, const InSeedRaw& r) {
+        return (KIND != KIND_ROW_T && a.cs_mode == 1u) ? mont_mul(r.hi, r.lo) : 0u;
+    }
     template <int LZ = 0>
-    static TOYNI_HD void in_scale(const PassArgs& a, const InSeedRaw& r, uint32_t (&x)[E1]) {
+    static TOYNI_HD void in_scale(const PassArgs& a, const InSeedRaw& r, uint32_t (&x)[E1]) { in_scale_by<LZ>(a, in_seed_finish(a, r), x); }
+    template <int LZ = 0>
+    static TOYNI_HD void in_scale_by(const PassArgs& a, uint32_t seed, uint32_t (&x)[E1]) {
         constexpr uint32_t NZ = E1 >> (LZ < LE1 ? LZ : LE1);  // zero-padded input: only these registers hold data
         if (KIND != KIND_ROW_T && a.cs_mode == 1u) {
-            uint32_t tw = mont_mul(r.hi, r.lo);
+            uint32_t tw = seed;
 #pragma unroll
             for (uint32_t i = 0; i < NZ; ++i) {
                 x[i] = mont_mul(x[i], tw);

@@ -84,6 +84,25 @@ inline const LaunchKnobs& launch_knobs() {
     return k;
 }
 
+// Whether every workgroup of a persistent KIND_COL launch stays on ONE column tile: workgroup b runs the tiles tile_order(v, ntiles),
+// v = b, b + grid, ..., and tile `bid` covers the columns (bid mod 2^(log_S - LC)) << LC of its prefix block.  The inter-pass twiddle
+// seeds and the forward coset seed of a thread depend on the tile through that column index alone, so where this holds the launcher
+// tells the kernel to look them up once per launch instead of once per tile (PassArgs::seeds_invariant).
+//   * grid >= ntiles: a workgroup has one tile;
+//   * otherwise v -> v + grid must move the tile index by a multiple of the tiles per prefix.  tile_order is the identity when ntiles
+//     is no multiple of 16, and otherwise permutes the low four bits of v only: with grid a multiple of 16 the step is exactly
+//     `grid` either way.  A paired launch whose grid is NOT a multiple of 16 changes those four bits from tile to tile and with
+//     them the column tile (for more than one tile per prefix): excluded, persistent_grid never makes one.
+constexpr bool seeds_launch_invariant(uint64_t grid, uint64_t ntiles, uint32_t log_S, uint32_t LC) {
+    if (grid == 0 || log_S < LC) return false;
+    if (grid >= ntiles) return true;
+    const uint32_t tiles_log = log_S - LC;
+    if (tiles_log == 0) return true;
+    if (tiles_log >= 32) return false;
+    if ((grid & (((uint64_t)1 << tiles_log) - 1)) != 0) return false;
+    return (ntiles & 15) != 0 || (grid & 15) == 0;
+}
+
 // latency = true: the SECOND plan of n = 2^21 / 2^22, two passes with a 2048-point three-step pass.  Rounds 2-4: 4-wide latency tiles
 // only -- one launch fewer for a lone transform -- while streaming launches kept the three-pass split below.  Round 5: the 2048-point
 // pass also has a STREAMING shape (16-wide tiles, 32 elements per thread), so n = 2^21 runs this plan for launches of every size

@@ -112,18 +112,27 @@ __global__ void __launch_bounds__(P::T, P::MIN_WAVES) ntt_pass_kernel(const Pass
         for (uint32_t j = tid; j < P::TW3_WORDS; j += P::T) lds_tw3[j] = P::tw3_global(a)[j];
         TOYNI_WAIT_VMEM0();  // the first tile's loads have landed: the loop is entered with no load pending on any path
         __syncthreads();
+        // Launch-invariant seeds (column passes, PassArgs::seeds_invariant): the seeds depend on the tile through its column index
+        // alone, and where the launcher has established that this workgroup never leaves its column tile they are finished here,
+        // once, and stay in registers across the loop -- no table gather and no seed product per tile.  Otherwise (uniform branch;
+        // a constant for the row kinds) every tile looks its own up, a tile ahead, as before.
+        const bool hoist = kind_of<P>() == KIND_COL && !P::SLAB && a.seeds_invariant != 0u;
+        typename P::Seeds seeds = P::seeds_finish(a, raw);
+        uint32_t inseed = P::in_seed_finish(a, inraw);
         while (true) {
             // The tile's loads (prefetch + seed lookups) were issued BEFORE the previous tile's E1 stores, and vmcnt
             // retires in issue order: allowing exactly the E1 youngest operations to stay outstanding retires every
             // load while the stores keep draining in the background.  (Ragged single-pass row tiles issue fewer
-            // stores, so they wait for everything.)
+            // stores, so they wait for everything.)  With the seed lookups hoisted the count stands: the youngest E1
+            // operations are still exactly the previous tile's stores, there are just fewer loads in front of them.
             static_assert(P::G2 * P::E2 == P::E1 && P::E1 <= 63, "stores per tile per thread");
             if constexpr (kind_of<P>() != KIND_ROW_N) TOYNI_WAIT_VMEM_ALLOW(P::E1);
             else TOYNI_WAIT_VMEM0();
             P::template load_tile<NPF, P::E1, LZ>(a, t, tid, x);
-            P::template in_scale<LZ>(a, inraw, x);  // forward coset FFT only (uniform branch)
+            if (!hoist) inseed = P::in_seed_finish(a, inraw);
+            P::template in_scale_by<LZ>(a, inseed, x);  // forward coset FFT only (uniform branch)
             P::template step1<LZ>(a, t, tid, x, lds, uni, lds_tw1, lds_tw3);
-            typename P::Seeds seeds = P::seeds_finish(a, raw);
+            if (!hoist) seeds = P::seeds_finish(a, raw);
 #pragma unroll
             for (uint32_t g = 0; g < P::G2; ++g) { TOYNI_PIN(seeds.g[g].a0); TOYNI_PIN(seeds.g[g].g); }  // materialised HERE
             TOYNI_SCHED_FENCE();
@@ -133,8 +142,10 @@ __global__ void __launch_bounds__(P::T, P::MIN_WAVES) ntt_pass_kernel(const Pass
             if (more) {
                 tn = P::tile_of(a, P::tile_order(vn, ntiles));
                 P::template load_tile<0, NPF, LZ>(a, tn, tid, x);  // prefetch
-                raw = P::seeds_issue(a, tn, tid);              // and the next tile's seed lookups, still ahead of the stores
-                inraw = P::in_seed_issue(a, tn, tid);
+                if (!hoist) {
+                    raw = P::seeds_issue(a, tn, tid);          // and the next tile's seed lookups, still ahead of the stores
+                    inraw = P::in_seed_issue(a, tn, tid);
+                }
             }
             TOYNI_SCHED_FENCE();
             TOYNI_LDS_BARRIER();  // this wave's LDS writes have landed; then the rendezvous
@@ -1834,8 +1845,25 @@ int grid_for(size_t items, int block = 256) {
 // per tile: with the next tile's 32 loads in flight it needs 128 VGPRs + 100 B of scratch; without them it fits)
 template <class P> constexpr int ext_prefetch() { return (kind_of<P>() == KIND_ROW_N && P::LM == 10) ? 0 : 32; }
 
+// The shapes whose kernel reads PassArgs::seeds_invariant: the two-step column shapes of ntt_pass_kernel.  Not their pieces-layout
+// variants (the flag costs those six SGPRs and with them a wave of occupancy; one rank's launches are a few tiles per workgroup),
+// and not the streaming 2048-point column shape of ntt_pass3s_kernel: its five seed registers, live across the loop, put the
+// blow-up-2 variant at 128 VGPRs + 16 B of scratch.
+template <class P> constexpr bool hoists_seeds() {
+    if constexpr (P::STEPS == 2) return kind_of<P>() == KIND_COL && !P::SLAB;
+    else return false;
+}
+
+template <class P> constexpr uint32_t log_tile_width() {
+    uint32_t l = 0;
+    while ((1u << l) < P::C) ++l;
+    return l;
+}
+
 template <class P, int LZ = 0>
-void launch_pass(unsigned grid, hipStream_t s, const PassArgs& a, uint32_t ntiles) {
+void launch_pass(unsigned grid, hipStream_t s, const PassArgs& args, uint32_t ntiles) {
+    PassArgs a = args;
+    if constexpr (hoists_seeds<P>()) a.seeds_invariant = seeds_launch_invariant(grid, ntiles, a.log_S, log_tile_width<P>()) ? 1u : 0u;
     if constexpr (P::STEPS == 3) {
         if constexpr (P::STREAM) hipLaunchKernelGGL((ntt_pass3s_kernel<P, LZ>), dim3(grid), dim3(P::T), 0, s, a, ntiles);
         else hipLaunchKernelGGL((ntt_pass3_kernel<P, LZ>), dim3(grid), dim3(P::T), 0, s, a, ntiles);
