@@ -21,7 +21,8 @@
  *            is a multiple of 4 takes 16-byte loads, others word loads)
  *   8 bytes  u64 pointers (toyni_ntt_device_u64, the narrow / widen pair) and the openings' d_out (row openings included)
  *   16 bytes the Ext folds' d_evals / d_out (one 16-byte access per Ext element; d_xs needs 4), the Ext DEEP combination's d_out (3h),
- *            the slab relayout's and the fused
+ *            the Ext fold round's d_evals / d_out and the Ext commit phase's d_layer0 / d_layers (toyni_fri_fold_commit_ext_device,
+ *            toyni_fri_commit_phase_ext_device, 3j), the slab relayout's and the fused
  *            slab rows' d_in / d_out, every Merkle d_levels / d_salts, the ChaCha20 fill's d_out
  *
  * Threading and streams: a context serialises the ENQUEUEING of its calls with an internal mutex, and keeps its
@@ -469,8 +470,9 @@ int toyni_column_scan_device(toyni_ntt_ctx* ctx, const uint32_t* d_num, size_t n
  *     codeword; with it the sequence
  *         batched inverse transform -> toyni_lde_device(batch = w) -> toyni_merkle_commit_rows_device
  *         -> toyni_poly_eval_ext_batch_device -> toyni_deep_combine_ext_device
- *         -> toyni_fri_fold_ext_device / toyni_merkle_commit_rows_device(TOYNI_ROWS_ROW_MAJOR, width = 4) per round
- *     stays on the device.  The quotient under Ext weights needs nothing new: toyni_air_quotient_device is linear in its weights, so
+ *         -> toyni_fri_commit_phase_ext_device (3j: every round's fold and commitment, the transcript behind a callback)
+ *         -> toyni_merkle_open_rows_device(TOYNI_ROWS_ROW_MAJOR, width = 4) per layer
+ *     stays on the device. The quotient under Ext weights needs nothing new: toyni_air_quotient_device is linear in its weights, so
  *     four calls with the coordinates of the weights write the quotient's four base columns, which join the DEEP combination as a
  *     second matrix (accumulate).  An Ext-valued polynomial held as four base columns q_0..q_3 (that quotient, or an Ext
  *     accumulator of 3i) needs no entry point of its own either: evaluate the four columns here and combine on the host,
@@ -554,6 +556,49 @@ int toyni_column_scan_ext_device(toyni_ntt_ctx* ctx, const toyni_ext_operand* nu
  * TOYNI_E_RANGE for count > 2^32, a stride < count or a pointer that is not 4-byte aligned.  count == 0 succeeds (and clears the count). */
 int toyni_batch_inverse_ext_device(const uint32_t* d_in, size_t in_stride, uint32_t* d_out, size_t out_stride, size_t count,
                                    uint32_t* d_zero_count, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 3j. The FRI commit phase over Ext-valued layers: what 3c's toyni_fri_fold_commit_device and toyni_fri_commit_phase_device are to a
+ *     base-field codeword, for the Ext codeword that toyni_deep_combine_ext_device (3h) leaves on the device.  An Ext layer is a
+ *     row-major matrix of width 4 (element i at ptr + 4 i, section 3), its commitment the row commitment of 3d: leaf i =
+ *     [salt_i (16)] || Ext::to_bytes (32), tree layout and opening record as 3d fixes them.  The leaf message 00 || leaf is 49 bytes
+ *     salted and 33 unsalted: ONE SHA-256 block, hashed in the fold's own sweep from the registers that hold the folded element.
+ *     Openings need nothing new: a layer is opened with toyni_merkle_open_rows_device(width = 4, TOYNI_ROWS_ROW_MAJOR), one call per
+ *     layer, on the layer's words in d_out / d_layers and its tree in d_levels.
+ *     Alignment: every device pointer here (d_evals, d_out, d_layer0, d_layers, d_salts, d_levels) is 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+/* One round: d_out = fri_fold_ext(d_evals) on the points x0 w_m^i with the Ext challenge beta, AND the Merkle tree of the folded
+ * layer in d_levels -- byte for byte what
+ *     toyni_fri_fold_ext_device(ctx, d_evals, d_out, m, beta, x0) followed by
+ *     toyni_merkle_commit_rows_device(d_out, m / 2, 4, TOYNI_ROWS_ROW_MAJOR, 0, d_salts, d_levels)
+ * write, in one launch less and without the second read of the layer.  m counts Ext elements (4 m words in, 2 m out);
+ * d_salts = (m / 2) x 16 bytes, or NULL for an unsalted tree; d_levels = toyni_merkle_total_digests(m / 2) x 32 bytes.  d_out must not
+ * overlap d_evals.  m == 0 succeeds and writes nothing; m == 2 gives a tree of one digest, the leaf.  Asynchronous on `stream`; on a
+ * warm context the call only enqueues a linear chain of kernels and can be captured into a HIP graph (caveat of section 4).
+ * Refused before anything is enqueued, the outputs untouched: TOYNI_E_NULL for a null ctx, d_evals, d_out, beta or d_levels;
+ * TOYNI_E_ODD_LENGTH for an odd m; TOYNI_E_RANGE for an m that is not a power of two or exceeds the context's n;
+ * TOYNI_E_ZERO_INVERSE for x0 == 0; TOYNI_E_RANGE for x0 >= p, a beta coordinate >= p, or a device pointer that is not 16-byte
+ * aligned.  All of these but "m exceeds n" are decided on the arguments alone, before the context is read. */
+int toyni_fri_fold_commit_ext_device(toyni_ntt_ctx* ctx, const uint32_t* d_evals, uint32_t* d_out, size_t m, const uint32_t beta[4], uint32_t x0,
+                                     const uint8_t* d_salts, uint8_t* d_levels, void* stream);
+/* The WHOLE fold loop in one blocking call: toyni_fri_commit_phase_device with Ext values and an Ext beta per round
+ * (squeeze_ext_challenge, src/transcript.rs:41-55: beta_out receives four canonical residues).  Everything else is 3c's call word for
+ * word: it blocks on every path (the stream has drained when it returns, also after a failing callback); the callback runs on the
+ * calling thread with the context locked (TOYNI_E_REENTRANT for an entry point on the same context from inside it) and is called once
+ * more after the last round with beta_out = NULL; each root reaches the host through the context's pinned notification word; h_roots
+ * and rounds_out as there; d_salts holds 16 bytes per leaf for every salted layer back to back, the final layer unsalted; round k
+ * folds on x0^(2^k).
+ *   d_layer0 : m0 Ext elements (4 m0 words)
+ *   d_layers : out, the folded layers back to back: 4 (m0/2 + m0/4 + ... + final_size) words, so every layer starts 16-byte aligned
+ *   d_levels : out, their trees back to back (toyni_merkle_total_digests(m_k) x 32 bytes each)
+ * Refused before anything is enqueued, the outputs untouched: TOYNI_E_NULL for a null ctx, d_layer0, callback, d_layers or d_levels;
+ * TOYNI_E_INVALID_SIZE for an m0 or final_size that is not a power of two, or m0 > n; TOYNI_E_ZERO_INVERSE for x0 == 0; TOYNI_E_RANGE
+ * for x0 >= p or a device pointer that is not 16-byte aligned.  A beta coordinate >= p from the callback ends the call with
+ * TOYNI_E_RANGE (the rounds before it stay committed). */
+typedef int (*toyni_fri_ext_challenge_fn)(void* user, unsigned round, const uint8_t* prev_root32, uint32_t beta_out[4]);
+int toyni_fri_commit_phase_ext_device(toyni_ntt_ctx* ctx, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size,
+                                      const uint8_t* d_salts, toyni_fri_ext_challenge_fn challenge, void* user, uint32_t* d_layers,
+                                      uint8_t* d_levels, uint8_t* h_roots, unsigned* rounds_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:

@@ -1,7 +1,18 @@
 #!/usr/bin/env python3
 """Per-round wall time of the FRI fold + commit rounds 2^21 -> 2^4 (diagnostic): where do the 2 ms of the phase go?
-Prints, per round: leaves of the folded layer, us for fold+commit enqueue + stream drain, us for the 32-byte root read-back."""
+Prints, per round: leaves of the folded layer, us for fold+commit enqueue + stream drain, us for the 32-byte root read-back.
+
+--ext: the commit phase over Ext-valued layers (include/toyni_hip.h 3j), m0 = 2^12, 2^16 and 2^20 Ext elements down to 16, salted:
+toyni_fri_commit_phase_ext_device against the sequence a caller had to write before it existed -- per round toyni_fri_fold_ext_device,
+toyni_merkle_commit_rows_device(width 4, row-major), toyni_stream_synchronize and a 32-byte toyni_memcpy_d2h of the root -- and one
+round of each at m = 2^20.  Both sides run the same betas on the same layer and must produce the same roots; they alternate within
+one process, after a warm-up of both, and each sample is a host clock around a call that ends blocked on the device.  The condition,
+written down before the first run: the single call is not slower (median) than the composed sequence at any of the three sizes.
+It is reported as measured; exit status 2 when it does not hold."""
+import argparse
+import ctypes
 import os
+import statistics
 import sys
 import time
 
@@ -43,5 +54,143 @@ def main():
     print(f"sum {tot * 1e3:.3f} ms")
 
 
+# ---- --ext ----
+EXT_SIZES = (12, 16, 20)
+EXT_FINAL = 16
+EXT_X0 = 7
+
+
+def ext_beta(rnd):
+    return [(1234567 * (rnd + 1) + 89 * k) % P for k in range(4)]
+
+
+def ext_phase_case(ctx, log_m0, reps, warmup, stream):
+    from toyni_amd._lib import FRI_EXT_CHALLENGE_FN, check
+    dev = torch.device("cuda", 0)
+    m0 = 1 << log_m0
+    halves = [m0 >> (k + 1) for k in range(log_m0 - EXT_FINAL.bit_length() + 1)]
+    assert halves[-1] == EXT_FINAL
+    layer0 = torch.randint(0, P, (4 * m0,), dtype=torch.int32, device=dev)
+    salts = torch.randint(0, 256, (sum(halves[:-1]), 16), dtype=torch.uint8, device=dev)
+    ndig = [lib.toyni_merkle_total_digests(h) for h in halves]
+    out = {name: (torch.empty(4 * sum(halves), dtype=torch.int32, device=dev), torch.empty((sum(ndig), 32), dtype=torch.uint8, device=dev))
+           for name in ("phase", "composed")}
+    betas = [(ctypes.c_uint32 * 4)(*ext_beta(k)) for k in range(len(halves))]
+
+    def _cb(_user, rnd, _root, beta_ptr):
+        if beta_ptr:
+            for k in range(4):
+                beta_ptr[k] = betas[rnd][k]
+        return 0
+
+    cb = FRI_EXT_CHALLENGE_FN(_cb)
+    roots = {name: (ctypes.c_uint8 * (32 * len(halves)))() for name in out}
+    rounds = ctypes.c_uint(0)
+
+    def phase():
+        layers, levels = out["phase"]
+        check(lib.toyni_fri_commit_phase_ext_device(ctx.handle, layer0.data_ptr(), m0, EXT_X0, EXT_FINAL, salts.data_ptr(), ctypes.cast(cb, ctypes.c_void_p),
+                                                    None, layers.data_ptr(), levels.data_ptr(), roots["phase"], ctypes.byref(rounds), stream), "phase")
+
+    def composed():
+        layers, levels = out["composed"]
+        cur, m, x, lo, dlo, slo = layer0.data_ptr(), m0, EXT_X0, layers.data_ptr(), levels.data_ptr(), salts.data_ptr()
+        for k, h in enumerate(halves):
+            last = k == len(halves) - 1
+            check(lib.toyni_fri_fold_ext_device(ctx.handle, cur, lo, m, betas[k], x, stream), "fold")
+            check(lib.toyni_merkle_commit_rows_device(lo, h, 4, toyni_amd.ROWS_ROW_MAJOR, 0, None if last else slo, dlo, stream), "commit")
+            check(lib.toyni_stream_synchronize(ctx.handle, stream), "synchronize")
+            check(lib.toyni_memcpy_d2h(ctypes.byref(roots["composed"], 32 * k), dlo + 32 * (ndig[k] - 1), 32), "root")
+            cur, m, x, lo, dlo, slo = lo, h, x * x % P, lo + 16 * h, dlo + 32 * ndig[k], slo + (0 if last else 16 * h)
+
+    samples = {"phase": [], "composed": []}
+    for r in range(warmup + reps):
+        for name, f in (("phase", phase), ("composed", composed)) if r % 2 == 0 else (("composed", composed), ("phase", phase)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            t1 = time.perf_counter()
+            if r >= warmup:
+                samples[name].append((t1 - t0) * 1e6)
+    torch.cuda.synchronize()
+    assert rounds.value == len(halves) and bytes(roots["phase"]) == bytes(roots["composed"]), "the two sequences disagree on the roots"
+    assert torch.equal(out["phase"][0], out["composed"][0]) and torch.equal(out["phase"][1], out["composed"][1]), "the two sequences disagree"
+    return len(halves), samples
+
+
+def ext_round_case(ctx, log_m, reps, warmup, stream):
+    from toyni_amd._lib import check
+    dev = torch.device("cuda", 0)
+    m = 1 << log_m
+    half = m // 2
+    layer = torch.randint(0, P, (4 * m,), dtype=torch.int32, device=dev)
+    salts = torch.randint(0, 256, (half, 16), dtype=torch.uint8, device=dev)
+    ndig = lib.toyni_merkle_total_digests(half)
+    out = {name: (torch.empty(4 * half, dtype=torch.int32, device=dev), torch.empty((ndig, 32), dtype=torch.uint8, device=dev)) for name in ("fused", "two calls")}
+    beta = (ctypes.c_uint32 * 4)(*ext_beta(0))
+
+    def fused():
+        o, lv = out["fused"]
+        check(lib.toyni_fri_fold_commit_ext_device(ctx.handle, layer.data_ptr(), o.data_ptr(), m, beta, EXT_X0, salts.data_ptr(), lv.data_ptr(), stream), "round")
+        check(lib.toyni_stream_synchronize(ctx.handle, stream), "synchronize")
+
+    def two_calls():
+        o, lv = out["two calls"]
+        check(lib.toyni_fri_fold_ext_device(ctx.handle, layer.data_ptr(), o.data_ptr(), m, beta, EXT_X0, stream), "fold")
+        check(lib.toyni_merkle_commit_rows_device(o.data_ptr(), half, 4, toyni_amd.ROWS_ROW_MAJOR, 0, salts.data_ptr(), lv.data_ptr(), stream), "commit")
+        check(lib.toyni_stream_synchronize(ctx.handle, stream), "synchronize")
+
+    samples = {"fused": [], "two calls": []}
+    for r in range(warmup + reps):
+        for name, f in (("fused", fused), ("two calls", two_calls)) if r % 2 == 0 else (("two calls", two_calls), ("fused", fused)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            t1 = time.perf_counter()
+            if r >= warmup:
+                samples[name].append((t1 - t0) * 1e6)
+    assert torch.equal(out["fused"][0], out["two calls"][0]) and torch.equal(out["fused"][1], out["two calls"][1]), "the round and the two calls disagree"
+    return samples
+
+
+def spread(v):
+    q = statistics.quantiles(v, n=10)
+    return f"median {statistics.median(v):9.1f} us   p10 {q[0]:9.1f}   p90 {q[-1]:9.1f}   min {min(v):9.1f}"
+
+
+def main_ext(reps, warmup):
+    ctx = toyni_amd.NttContext(1 << max(EXT_SIZES))
+    stream = torch.cuda.current_stream().cuda_stream or None
+    print(f"Ext FRI commit phase, final_size {EXT_FINAL}, salted, x0 {EXT_X0}; {reps} alternating samples after {warmup} warm-up rounds of both; "
+          f"host clock around blocking calls; device {torch.cuda.get_device_name(0)}")
+    verdicts = []
+    for log_m0 in EXT_SIZES:
+        rounds, s = ext_phase_case(ctx, log_m0, reps, warmup, stream)
+        a, b = statistics.median(s["phase"]), statistics.median(s["composed"])
+        print(f"m0 = 2^{log_m0} ({rounds} rounds)")
+        print(f"  toyni_fri_commit_phase_ext_device          {spread(s['phase'])}")
+        print(f"  fold_ext + commit_rows + sync + d2h / round {spread(s['composed'])}")
+        print(f"  composed / phase = {b / a:.3f}   ({(b - a) / rounds:+.1f} us per round)")
+        verdicts.append((log_m0, a, b))
+    s = ext_round_case(ctx, 20, reps, warmup, stream)
+    a, b = statistics.median(s["fused"]), statistics.median(s["two calls"])
+    print("one round at m = 2^20 (2^19 leaves), each followed by a stream synchronisation")
+    print(f"  toyni_fri_fold_commit_ext_device           {spread(s['fused'])}")
+    print(f"  fold_ext + commit_rows                     {spread(s['two calls'])}")
+    print(f"  two calls / fused = {b / a:.3f}")
+    failed = [(l, a, b) for l, a, b in verdicts if a > b]
+    if failed:
+        for l, a, b in failed:
+            print(f"CONDITION NOT MET at m0 = 2^{l}: the single call took {a:.1f} us (median), the composed sequence {b:.1f} us")
+        return 2
+    print("CONDITION MET: the single call is not slower (median) than the composed sequence at 2^12, 2^16 and 2^20")
+    return 0
+
+
 if __name__ == "__main__":
-    main()
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--ext", action="store_true", help="the Ext commit phase against the composed sequence (see above)")
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=10)
+    args = ap.parse_args()
+    sys.exit(main_ext(args.reps, args.warmup) if args.ext else main())

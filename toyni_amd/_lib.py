@@ -46,6 +46,8 @@ p_u32 = ctypes.POINTER(ctypes.c_uint32)
 
 # toyni_fri_challenge_fn: int (*)(void* user, unsigned round, const uint8_t* prev_root32, uint32_t* beta_out)
 FRI_CHALLENGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_uint, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint32))
+# toyni_fri_ext_challenge_fn: the same with uint32_t beta_out[4]
+FRI_EXT_CHALLENGE_FN = FRI_CHALLENGE_FN
 
 # name -> (restype, argtypes); mirrors include/toyni_hip.h line by line
 SIGNATURES = {
@@ -132,6 +134,10 @@ SIGNATURES = {
     "toyni_column_scan_ext_tile": (c_size, []),
     "toyni_column_scan_ext_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_size, c_size, c_int, c_void_p, c_void_p, c_void_p]),
     "toyni_batch_inverse_ext_device": (c_int, [c_void_p, c_size, c_void_p, c_size, c_size, c_void_p, c_void_p]),
+    # section 3j
+    "toyni_fri_fold_commit_ext_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_void_p, c_u32, c_void_p, c_void_p, c_void_p]),
+    "toyni_fri_commit_phase_ext_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                  c_void_p, ctypes.POINTER(ctypes.c_uint), c_void_p]),
     # section 3c
     "toyni_fri_fold_commit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

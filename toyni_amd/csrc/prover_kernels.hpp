@@ -1068,6 +1068,22 @@ TOYNI_HD Ext4 poly_ext_final_thread(const PolyExtArgs& a, uint32_t col, uint32_t
     return poly_ext_times_power(pw, r, t);
 }
 
+// ---- one output of an Ext FRI round that commits what it folds (include/toyni_hip.h 3j) ----
+// fold_ext_one, then the row leaf of the folded element -- 00 || salt(16) || Ext::to_bytes(32): width 4, ONE SHA-256 block either way
+// (12 or 8 data words + padding + length) -- hashed from the registers the fold left it in.  `salt_words`: 4 LE words when SALTED,
+// not read otherwise.  What fri_fold_ext_commit_kernel runs per thread, and what tests/emu steps on the CPU.
+struct FoldExtLeaf { Ext4 folded; Digest leaf; };
+template <bool SALTED>
+TOYNI_HD FoldExtLeaf fold_ext_commit_one(const Ext4& a, const Ext4& b, uint32_t scaleR, const ExtFactor& beta_half, const uint32_t* salt_words) {
+    FoldExtLeaf r;
+    r.folded = fold_ext_one(a, b, scaleR, beta_half);
+    const Ext4 v = r.folded;
+    r.leaf = merkle_row_leaf<SALTED>(4u, salt_words, [&v](int, uint32_t (&c)[8]) {   // the one chunk: columns 0 .. 3, the rest ignored
+        c[0] = v.c[0]; c[1] = v.c[1]; c[2] = v.c[2]; c[3] = v.c[3];
+    });
+    return r;
+}
+
 // ---- Merkle openings (src/merkle.rs:50-80, src/fibonacci.rs:366-375) ----
 // record of one opening: depth x 32 path bytes | 16 salt bytes (zero when unsalted) | value as 8 LE bytes | depth position bytes
 // (1 = the sibling is the LEFT input of the node hash), padding zero to a multiple of 8

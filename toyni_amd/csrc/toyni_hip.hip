@@ -1332,6 +1332,32 @@ __global__ void __launch_bounds__(256) fri_fold_ext_kernel(const FoldExtArgs fa)
     }
 }
 
+// The same sweep with the folded layer's leaf hashes in it (fold_ext_commit_one, prover_kernels.hpp; include/toyni_hip.h 3j):
+// leaves[i] = SHA256(00 || salt_i || out[i].to_bytes()), the row leaf of width 4 that toyni_merkle_commit_rows_device would compute from
+// a second read of the layer.  One output and ONE compression per thread, like fri_fold_kernel<.., COMMIT>: hash-bound, so as wide as
+// the leaf kernel and never shaped as a stream.
+template <bool SALTED>
+__global__ void __launch_bounds__(256) fri_fold_ext_commit_kernel(const FoldExtArgs fa, const uint4* __restrict__ salts, Digest* __restrict__ leaves) {
+    const FoldArgs& f = fa.base;
+    const uint64_t half = f.half;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint4* ea = reinterpret_cast<const uint4*>(f.evals);
+    const uint4* eb = ea + half;
+    uint4* o = reinterpret_cast<uint4*>(f.out);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < half; i += stride) {
+        const uint32_t scaleR = mont_mul(subdomain_mont(f.dom, (uint32_t)i), f.coef);
+        const uint4 a = ea[i], b = eb[i];
+        uint32_t sw[4] = {0u, 0u, 0u, 0u};
+        if constexpr (SALTED) {
+            const uint4 s = salts[i];
+            sw[0] = s.x; sw[1] = s.y; sw[2] = s.z; sw[3] = s.w;
+        }
+        const FoldExtLeaf r = fold_ext_commit_one<SALTED>(Ext4{{a.x, a.y, a.z, a.w}}, Ext4{{b.x, b.y, b.z, b.w}}, scaleR, fa.beta_half, sw);
+        o[i] = make_uint4(r.folded.c[0], r.folded.c[1], r.folded.c[2], r.folded.c[3]);
+        leaves[i] = r.leaf;
+    }
+}
+
 // The same for large layers in the shape of fri_fold_stream_kernel: T-thread workgroups, U load pairs in flight per lane, U * T
 // consecutive elements per workgroup and iteration, non-temporal when the layer is far larger than the Infinity Cache.
 template <bool NT, int T, int U>
@@ -3148,19 +3174,19 @@ static bool poll_until(volatile uint32_t* flag, uint32_t want, double seconds) {
     }
 }
 
-// The fold loop of the commit phase, src/fibonacci.rs:222-245, with the transcript on the caller's side of a callback.
-int toyni_fri_commit_phase_device(toyni_ntt_ctx* c, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size,
-                                  const uint8_t* d_salts, toyni_fri_challenge_fn challenge, void* user, uint32_t* d_layers,
-                                  uint8_t* d_levels, uint8_t* h_roots, unsigned* rounds_out, void* stream) {
-    if (!c || !d_layer0 || !challenge || !d_layers || !d_levels) return TOYNI_E_NULL;
-    if (!is_pow2(m0) || !is_pow2(final_size) || final_size < 1 || m0 > c->n) return TOYNI_E_INVALID_SIZE;
-    if (x0 == 0 || x0 >= BB_P) return TOYNI_E_RANGE;
-    if (((uintptr_t)d_levels & 15) || ((uintptr_t)d_salts & 15)) return TOYNI_E_RANGE;
+// The fold loop of the commit phase, src/fibonacci.rs:222-245, with the transcript on the caller's side of a callback.  One loop for
+// both element types: `words` = u32 words per layer element (1 base field, 4 Ext), Beta = uint32_t or ExtBeta,
+//   challenge(round, prev_root32 or nullptr, Beta* or nullptr) -> int      the caller's callback
+//   enqueue_round(cur, out, m, beta, x, salts, levels, notify, seq) -> int  one fold + commit; refuses a beta outside the field
+// The arguments have been checked by the entry point.
+extern "C++" template <class Beta, class Challenge, class Round>
+static int commit_phase_loop(toyni_ntt_ctx* c, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size, size_t words,
+                             const uint8_t* d_salts, uint32_t* d_layers, uint8_t* d_levels, uint8_t* h_roots, unsigned* rounds_out,
+                             hipStream_t s, Challenge&& challenge, Round&& enqueue_round) {
     if (rounds_out) *rounds_out = 0;
     if (m0 <= final_size) return TOYNI_OK;
     TOYNI_CTX_LOCK(c);
     DeviceGuard guard(c->device);
-    hipStream_t s = (hipStream_t)stream;
     if (!c->h_root) {
         // 32-byte root, then the sequence word, in pinned host memory that the device writes mid-stream with a system-scope release
         // store: that needs fine-grained (coherent) memory, so it is asked for explicitly rather than left to HIP_HOST_COHERENT.
@@ -3186,19 +3212,18 @@ int toyni_fri_commit_phase_device(toyni_ntt_ctx* c, const uint32_t* d_layer0, si
     unsigned round = 0;
     bool have_root = false;
     for (size_t m = m0; m > final_size; m >>= 1, ++round) {
-        uint32_t beta = 0;
+        Beta beta{};
         int rc;
         {
             CallbackScope scope(c);
-            rc = challenge(user, round, have_root ? c->h_root : nullptr, &beta);
+            rc = challenge(round, have_root ? c->h_root : nullptr, &beta);
         }
         if (rc) return rc;
-        if (beta >= BB_P) return TOYNI_E_RANGE;
         const size_t half = m >> 1;
         const bool last = half == final_size;
         const size_t digests = toyni_merkle_total_digests(half);
         const uint32_t seq = ++c->root_seq ? c->root_seq : ++c->root_seq;   // never 0
-        if ((rc = enqueue_fold_commit(c, cur, out, m, beta, x, s, last ? nullptr : salts, levels, c->d_root_notify, seq))) return rc;
+        if ((rc = enqueue_round(cur, out, m, beta, x, last ? nullptr : salts, levels, c->d_root_notify, seq))) return rc;
         // The tree's last kernel writes the root and then `seq` into pinned host memory; everything enqueued before it on `s` has
         // completed by then (stream order).  Polling costs ~2 us where a 32-byte copy plus a stream synchronisation costs ~16.
         if (!poll_until(flag, seq, 2.0)) {
@@ -3209,7 +3234,7 @@ int toyni_fri_commit_phase_device(toyni_ntt_ctx* c, const uint32_t* d_layer0, si
         have_root = true;
         if (h_roots) std::memcpy(h_roots + (size_t)round * 32, c->h_root, 32);
         cur = out;
-        out += half;
+        out += half * words;
         levels += digests * 32;
         if (salts && !last) salts += half * 16;
         x = (uint32_t)((uint64_t)x * x % BB_P);   // the squared domain of the next layer, :228-231
@@ -3218,7 +3243,83 @@ int toyni_fri_commit_phase_device(toyni_ntt_ctx* c, const uint32_t* d_layer0, si
     HIPCHK(hipStreamSynchronize(s));   // the call is blocking: the layers and trees are complete when it returns
     reclaim_after_sync(c, s);
     CallbackScope scope(c);
-    return challenge(user, round, c->h_root, nullptr);   // the transcript absorbs the last commitment too, :242-243
+    return challenge(round, c->h_root, static_cast<Beta*>(nullptr));   // the transcript absorbs the last commitment too, :242-243
+}
+
+int toyni_fri_commit_phase_device(toyni_ntt_ctx* c, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size,
+                                  const uint8_t* d_salts, toyni_fri_challenge_fn challenge, void* user, uint32_t* d_layers,
+                                  uint8_t* d_levels, uint8_t* h_roots, unsigned* rounds_out, void* stream) {
+    if (!c || !d_layer0 || !challenge || !d_layers || !d_levels) return TOYNI_E_NULL;
+    if (!is_pow2(m0) || !is_pow2(final_size) || final_size < 1 || m0 > c->n) return TOYNI_E_INVALID_SIZE;
+    if (x0 == 0 || x0 >= BB_P) return TOYNI_E_RANGE;
+    if (((uintptr_t)d_levels & 15) || ((uintptr_t)d_salts & 15)) return TOYNI_E_RANGE;
+    hipStream_t s = (hipStream_t)stream;
+    return commit_phase_loop<uint32_t>(
+        c, d_layer0, m0, x0, final_size, 1, d_salts, d_layers, d_levels, h_roots, rounds_out, s,
+        [&](unsigned round, const uint8_t* root, uint32_t* beta) { return challenge(user, round, root, beta); },
+        [&](const uint32_t* cur, uint32_t* out, size_t m, uint32_t beta, uint32_t x, const uint8_t* salts, uint8_t* levels, uint32_t* notify,
+            uint32_t seq) {
+            if (beta >= BB_P) return (int)TOYNI_E_RANGE;
+            return enqueue_fold_commit(c, cur, out, m, beta, x, s, salts, levels, notify, seq);
+        });
+}
+
+// ---- the same round and the same phase over Ext-valued layers (include/toyni_hip.h 3j) ----
+// fold (+ the width-4 row leaves in the same sweep), then the node levels and the root's notification through enqueue_merkle_upper.
+// Arguments checked by the caller: m >= 2 a power of two <= n, x0 in [1, p), 16-byte aligned pointers.
+static int enqueue_fold_commit_ext(toyni_ntt_ctx* c, const uint32_t* d_evals, uint32_t* d_out, size_t m, const ExtFactor& beta_half, uint32_t x0,
+                                   hipStream_t s, const uint8_t* d_salts, uint8_t* d_levels, uint32_t* notify, uint32_t seq) {
+    FoldExtArgs fa{};
+    fa.beta_half = beta_half;
+    fa.base.evals = d_evals;
+    fa.base.out = d_out;
+    fa.base.dom = sub_domain(c->plan, c->d_inv, c->plan.log_n - ilog2(m));
+    fa.base.coef = to_mont_host(bb_inv_host(x0));
+    fa.base.half = m / 2;
+    const dim3 grid(grid_for(fa.base.half)), block(256);
+    Digest* leaves = reinterpret_cast<Digest*>(d_levels);
+    if (d_salts) hipLaunchKernelGGL((fri_fold_ext_commit_kernel<true>), grid, block, 0, s, fa, reinterpret_cast<const uint4*>(d_salts), leaves);
+    else hipLaunchKernelGGL((fri_fold_ext_commit_kernel<false>), grid, block, 0, s, fa, static_cast<const uint4*>(nullptr), leaves);
+    return enqueue_merkle_upper(d_levels, m / 2, s, notify, seq);
+}
+
+int toyni_fri_fold_commit_ext_device(toyni_ntt_ctx* c, const uint32_t* d_evals, uint32_t* d_out, size_t m, const uint32_t beta[4], uint32_t x0,
+                                     const uint8_t* d_salts, uint8_t* d_levels, void* stream) {
+    // every refusal that the arguments alone decide comes before the context is read
+    if (!c || !d_evals || !d_out || !beta || !d_levels) return TOYNI_E_NULL;
+    if (m % 2) return TOYNI_E_ODD_LENGTH;
+    if (!is_pow2(m) && m) return TOYNI_E_RANGE;
+    if (x0 == 0) return TOYNI_E_ZERO_INVERSE;
+    if (((uintptr_t)d_evals | (uintptr_t)d_out | (uintptr_t)d_levels | (uintptr_t)d_salts) & 15) return TOYNI_E_RANGE;   // 16-byte accesses
+    ExtFactor beta_half;
+    if (x0 >= BB_P || !ext_beta_half(beta, &beta_half)) return TOYNI_E_RANGE;
+    if (m == 0) return TOYNI_OK;
+    if (m > c->n) return TOYNI_E_RANGE;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    return enqueue_fold_commit_ext(c, d_evals, d_out, m, beta_half, x0, (hipStream_t)stream, d_salts, d_levels, nullptr, 0);
+}
+
+struct ExtBeta { uint32_t v[4]; };
+int toyni_fri_commit_phase_ext_device(toyni_ntt_ctx* c, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size,
+                                      const uint8_t* d_salts, toyni_fri_ext_challenge_fn challenge, void* user, uint32_t* d_layers,
+                                      uint8_t* d_levels, uint8_t* h_roots, unsigned* rounds_out, void* stream) {
+    if (!c || !d_layer0 || !challenge || !d_layers || !d_levels) return TOYNI_E_NULL;
+    if (!is_pow2(m0) || !is_pow2(final_size) || final_size < 1) return TOYNI_E_INVALID_SIZE;
+    if (x0 == 0) return TOYNI_E_ZERO_INVERSE;
+    if (x0 >= BB_P) return TOYNI_E_RANGE;
+    if (((uintptr_t)d_layer0 | (uintptr_t)d_layers | (uintptr_t)d_levels | (uintptr_t)d_salts) & 15) return TOYNI_E_RANGE;
+    if (m0 > c->n) return TOYNI_E_INVALID_SIZE;
+    hipStream_t s = (hipStream_t)stream;
+    return commit_phase_loop<ExtBeta>(
+        c, d_layer0, m0, x0, final_size, 4, d_salts, d_layers, d_levels, h_roots, rounds_out, s,
+        [&](unsigned round, const uint8_t* root, ExtBeta* beta) { return challenge(user, round, root, beta ? beta->v : nullptr); },
+        [&](const uint32_t* cur, uint32_t* out, size_t m, const ExtBeta& beta, uint32_t x, const uint8_t* salts, uint8_t* levels,
+            uint32_t* notify, uint32_t seq) {
+            ExtFactor beta_half;
+            if (!ext_beta_half(beta.v, &beta_half)) return (int)TOYNI_E_RANGE;
+            return enqueue_fold_commit_ext(c, cur, out, m, beta_half, x, s, salts, levels, notify, seq);
+        });
 }
 
 static DomainArgs domain_args(toyni_ntt_ctx* c, unsigned log_m, uint32_t shift) {

@@ -20,6 +20,15 @@ def fri_commit_phase_device(ctx, d_layer0: int, m0: int, x0: int, final_size: in
     """The fold loop of the commit phase (src/fibonacci.rs:222-245) in one call.  `challenge(round, prev_root: bytes | None,
     want_beta: bool) -> int` is the caller's transcript: absorb prev_root when it is not None, return the squeezed beta when
     want_beta (anything otherwise).  Returns the list of roots (bytes), one per round."""
+    def store(beta_ptr, beta):
+        beta_ptr[0] = int(beta)
+
+    return _commit_phase(lib.toyni_fri_commit_phase_device, store, ctx, d_layer0, m0, x0, final_size, d_salts, challenge, d_layers, d_levels, stream)
+
+
+def _commit_phase(entry, store_beta, ctx, d_layer0, m0, x0, final_size, d_salts, challenge, d_layers, d_levels, stream):
+    """The commit-phase call of either element type: `entry` the library's loop, `store_beta(beta_ptr, beta)` writes what the
+    caller's transcript squeezed (one word, or four)."""
     from ._lib import FRI_CHALLENGE_FN
     failure = []
 
@@ -28,7 +37,7 @@ def fri_commit_phase_device(ctx, d_layer0: int, m0: int, x0: int, final_size: in
             root = bytes(root_ptr[:32]) if root_ptr else None
             beta = challenge(int(rnd), root, bool(beta_ptr))
             if beta_ptr:
-                beta_ptr[0] = int(beta)
+                store_beta(beta_ptr, beta)
             return 0
         except BaseException as e:  # noqa: BLE001  (nothing may unwind through the C frames -- KeyboardInterrupt included: ctypes
             failure.append(e)       # would print and swallow it, return 0, and the C loop would go on with beta = 0; re-raised below)
@@ -38,12 +47,36 @@ def fri_commit_phase_device(ctx, d_layer0: int, m0: int, x0: int, final_size: in
     rounds = ctypes.c_uint(0)
     max_rounds = max(0, (m0 // max(final_size, 1)).bit_length() - 1)
     roots = np.zeros(max(max_rounds, 1) * 32, dtype=np.uint8)
-    rc = lib.toyni_fri_commit_phase_device(ctx.handle, d_layer0, m0, x0, final_size, d_salts or None, ctypes.cast(cb, ctypes.c_void_p), None,
-                                           d_layers, d_levels, roots.ctypes.data, ctypes.byref(rounds), stream or None)
+    rc = entry(ctx.handle, d_layer0, m0, x0, final_size, d_salts or None, ctypes.cast(cb, ctypes.c_void_p), None,
+               d_layers, d_levels, roots.ctypes.data, ctypes.byref(rounds), stream or None)
     if failure:
         raise failure[0]
     check(rc, "GPU FRI commit phase failed")
     return [roots[32 * k:32 * k + 32].tobytes() for k in range(rounds.value)]
+
+
+def fri_fold_commit_ext_device(ctx, d_evals: int, d_out: int, m: int, beta4, x0: int, d_salts: int, d_levels: int, stream: int = 0) -> None:
+    """fold a layer of m Ext elements with the Ext challenge beta4 and commit the folded layer (row leaves of width 4, all tree levels
+    to d_levels) in one call (include/toyni_hip.h 3j)."""
+    b = np.ascontiguousarray(beta4, dtype=np.uint32)
+    assert b.size == 4
+    check(lib.toyni_fri_fold_commit_ext_device(ctx.handle, d_evals, d_out, m, b.ctypes.data, x0, d_salts or None, d_levels, stream or None),
+          "GPU fold + commit (Ext) failed")
+
+
+def fri_commit_phase_ext_device(ctx, d_layer0: int, m0: int, x0: int, final_size: int, d_salts: int, challenge, d_layers: int, d_levels: int,
+                                stream: int = 0):
+    """fri_commit_phase_device over Ext-valued layers: `challenge(round, prev_root: bytes | None, want_beta: bool)` returns four
+    ints, the coordinates of the squeezed Ext beta, when want_beta.  Returns the list of roots (bytes), one per round."""
+    def store(beta_ptr, beta):
+        c = [int(v) for v in beta]
+        if len(c) != 4:
+            raise ValueError("an Ext challenge has four coordinates")
+        for k in range(4):
+            beta_ptr[k] = c[k]
+
+    return _commit_phase(lib.toyni_fri_commit_phase_ext_device, store, ctx, d_layer0, m0, x0, final_size, d_salts, challenge, d_layers, d_levels,
+                         stream)
 
 
 def fib_quotient_device(ctx, d_trace_lde: int, d_c_evals: int, d_q_evals: int, log_blowup: int, shift: int, stream: int = 0) -> None:
