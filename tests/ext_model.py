@@ -105,9 +105,16 @@ def poly_eval_ext_batch_model(columns, points):
     return out
 
 
-def deep_ext_model(m, terms, blowup, shift, z):
+def deep_denominators(n, shift, z):
+    """(n, 4) uint64: 1 / (x_i - z) on the coset, 0 where x_i = z."""
+    z = tuple(int(v) for v in z)
+    return np.array(batch_inverse([sub(embed(x), z) for x in coset_points(n, shift)]), dtype=np.uint64)
+
+
+def deep_ext_model(m, terms, blowup, shift, z, inv=None):
     """m: (width, N) canonical residues; terms: (column, rotation, alpha4, value4); z: Ext.  -> (N, 4) uint32:
-    d_i = sum_t alpha_t (M(column_t, i + rotation_t * blowup) - value_t) / (x_i - z), and 0 where x_i = z."""
+    d_i = sum_t alpha_t (M(column_t, i + rotation_t * blowup) - value_t) / (x_i - z), and 0 where x_i = z.  inv: deep_denominators(N,
+    shift, z) when the caller has them already (several matrices over one z)."""
     m = np.asarray(m, dtype=np.uint64)
     n = m.shape[1]
     p = np.uint64(P)
@@ -117,6 +124,6 @@ def deep_ext_model(m, terms, blowup, shift, z):
         diff[:, 0] = np.roll(m[c], -(rot * blowup) % n)
         diff = (diff + np.array(neg(tuple(int(v) for v in value)), dtype=np.uint64)) % p
         num = (num + vmul(diff, np.array([int(v) for v in alpha], dtype=np.uint64))) % p
-    z = tuple(int(v) for v in z)
-    inv = batch_inverse([sub(embed(x), z) for x in coset_points(n, shift)])
-    return vmul(num, np.array(inv, dtype=np.uint64)).astype(np.uint32)
+    if inv is None:
+        inv = deep_denominators(n, shift, z)
+    return vmul(num, inv).astype(np.uint32)
