@@ -16,12 +16,17 @@
 #include <cstdint>
 #include <cstdio>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "ntt_plan.hpp"
 #include "prover_kernels.hpp"
+#include "contract_case.hpp"
 
 using namespace toyni;
+
+// `saturated` as the only argument runs, instead of the cases above, a program whose every product is (p - 1)^2: every cell p - 1,
+// the constant and the weight SAT_X, the plain value whose Montgomery form is p - 1 (same record format)
 
 static uint64_t sm_state = 0xA1A1A1ull;
 static uint64_t splitmix() {
@@ -76,7 +81,9 @@ static std::vector<Insn> random_program(uint32_t nregs, uint32_t length, const s
     return p;
 }
 
-static void air_case(int log_N, int log_blowup, uint32_t shift, std::vector<Mat> mats, const std::vector<Insn>& prog, uint32_t nweights, bool zh_classes) {
+static void air_case(int log_N, int log_blowup, uint32_t shift, std::vector<Mat> mats, const std::vector<Insn>& prog, uint32_t nweights, bool zh_classes,
+                     bool sat = false) {
+    TOYNI_CONTRACT_TAG("air_eval_group log_N=%d log_blowup=%d ninsns=%zu zh_classes=%d sat=%d", log_N, log_blowup, prog.size(), (int)zh_classes, (int)sat);
     NttPlan plan;
     if (!build_plan(log_N, plan)) { std::printf("FAIL plan\n"); return; }
     const uint64_t N = 1ull << log_N, n = N >> log_blowup;
@@ -86,10 +93,10 @@ static void air_case(int log_N, int log_blowup, uint32_t shift, std::vector<Mat>
         m.m = m.store + m.offset;
         for (size_t k = 0; k < words; ++k) m.m[k] = 0xFFFFFFF0u;
         for (uint32_t c = 0; c < m.width; ++c)
-            for (uint64_t i = 0; i < N; ++i) m.m[c * m.stride + i] = draw(splitmix());
+            for (uint64_t i = 0; i < N; ++i) m.m[c * m.stride + i] = sat ? BB_P - 1u : draw(splitmix());
     }
     std::vector<uint32_t> weights(nweights);
-    for (uint32_t k = 0; k < nweights; ++k) weights[k] = draw(k + 3);
+    for (uint32_t k = 0; k < nweights; ++k) weights[k] = sat ? SAT_X : draw(k + 3);
     // what toyni_air_program_create and toyni_air_quotient_device prepare
     std::vector<AirInsn> dev(prog.size());
     uint32_t nregs = 0, divides = 0;
@@ -160,7 +167,16 @@ static void air_case(int log_N, int log_blowup, uint32_t shift, std::vector<Mat>
     for (Mat& m : mats) ::operator delete(m.store, std::align_val_t(16));
 }
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "saturated") {
+        // cell * SAT_X, that times the next row's cell, emitted under weight SAT_X: the first product undivided, the second divided by Z_H under both weights
+        const std::vector<Insn> prog = {{AIR_OP_CELL, 0, 0, 0, 0}, {AIR_OP_CONST, 1, 0, 0, SAT_X}, {AIR_OP_MUL, 2, 0, 1, 0}, {AIR_OP_CELL, 0, 1, 0, 1},
+                                        {AIR_OP_MUL, 3, 2, 0, 0}, {AIR_OP_EMIT, 0, 2, 1, 0}, {AIR_OP_EMIT, 0, 3, 0, 1}, {AIR_OP_EMIT, 0, 3, 0, 0}};
+        for (int log_blowup : {0, 2})
+            for (bool classes : {true, false}) air_case(6, log_blowup, SAT_X, {Mat{2, 64, 0, nullptr, nullptr}}, prog, 2, classes, true);
+        std::printf("DONE\n");
+        return 0;
+    }
     const int log_Ns[] = {1, 2, 3, 6};
     uint32_t k = 0;
     for (int log_N : log_Ns) {

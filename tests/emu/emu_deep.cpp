@@ -14,12 +14,17 @@
 #include <cstdint>
 #include <cstdio>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "ntt_plan.hpp"
 #include "prover_kernels.hpp"
+#include "contract_case.hpp"
 
 using namespace toyni;
+
+// `saturated` as the only argument runs, instead of the cases above, the ones whose every product is (p - 1)^2: every data word
+// p - 1 and every weight, claim and point SAT_X, the plain value whose Montgomery form is p - 1 (same record format)
 
 static uint64_t sm_state = 0xD1CEDEE9ull;
 static uint64_t splitmix() {
@@ -40,7 +45,8 @@ static uint32_t draw(uint64_t k) {   // {0, 1, p - 1, random}
 struct Term { uint32_t column, rotation, alpha, value; };
 
 // z_at >= 0: z is the coset's point of that index
-static void deep_case(int log_N, int log_blowup, uint32_t width, uint32_t nterms, uint32_t pad, uint32_t offset_words, long z_at) {
+static void deep_case(int log_N, int log_blowup, uint32_t width, uint32_t nterms, uint32_t pad, uint32_t offset_words, long z_at, bool sat = false) {
+    TOYNI_CONTRACT_TAG("deep_combine_group log_N=%d width=%u nterms=%u sat=%d", log_N, width, nterms, (int)sat);
     NttPlan plan;
     if (!build_plan(log_N, plan)) { std::printf("FAIL plan\n"); return; }
     const uint64_t N = 1ull << log_N, rows = N >> log_blowup, col_stride = N + pad;
@@ -52,8 +58,8 @@ static void deep_case(int log_N, int log_blowup, uint32_t width, uint32_t nterms
         terms[t].column = (uint32_t)(splitmix() % width);
         // rotations up to rows - 1: (i + rotation * B) passes N for the later points
         terms[t].rotation = (t % 3 == 2) ? (uint32_t)(rows - 1) : (uint32_t)(splitmix() % rows);
-        terms[t].alpha = draw(t + nterms);
-        terms[t].value = draw(t + 2 * nterms + 1);
+        terms[t].alpha = sat ? SAT_X : draw(t + nterms);
+        terms[t].value = sat ? SAT_X : draw(t + 2 * nterms + 1);
     }
     if (nterms >= 2) terms[1] = Term{terms[0].column, terms[0].rotation, terms[1].alpha, terms[1].value};   // a repeated (column, rotation)
     const size_t words = (size_t)(width - 1) * col_stride + N;
@@ -61,7 +67,7 @@ static void deep_case(int log_N, int log_blowup, uint32_t width, uint32_t nterms
     uint32_t* m = store + offset_words;
     for (size_t k = 0; k < words; ++k) m[k] = 0xFFFFFFF0u;   // the slack between N and col_stride: never read (>= p would show)
     for (uint32_t c = 0; c < width; ++c)
-        for (uint64_t i = 0; i < N; ++i) m[c * col_stride + i] = draw(splitmix());
+        for (uint64_t i = 0; i < N; ++i) m[c * col_stride + i] = sat ? BB_P - 1u : draw(splitmix());
 
     // what toyni_deep_combine_device prepares
     std::vector<DeepTerm> table(nterms);
@@ -108,11 +114,12 @@ static void deep_case(int log_N, int log_blowup, uint32_t width, uint32_t nterms
     ::operator delete(store, std::align_val_t(16));
 }
 
-static void poly_case(size_t ncoeffs, size_t stride, uint32_t batch, uint32_t npoints) {
+static void poly_case(size_t ncoeffs, size_t stride, uint32_t batch, uint32_t npoints, bool sat = false) {
+    TOYNI_CONTRACT_TAG("poly_batch ncoeffs=%zu batch=%u npoints=%u sat=%d", ncoeffs, batch, npoints, (int)sat);
     std::vector<uint32_t> coeffs(batch ? (size_t)(batch - 1) * stride + ncoeffs : 0);   // exactly the words the layout owns
     for (auto& c : coeffs) c = 0xFFFFFFF0u;
     for (uint32_t b = 0; b < batch; ++b)
-        for (size_t i = 0; i < ncoeffs; ++i) coeffs[b * stride + i] = draw(splitmix());
+        for (size_t i = 0; i < ncoeffs; ++i) coeffs[b * stride + i] = sat ? BB_P - 1u : draw(splitmix());
     uint32_t points[POLY_MAX_POINTS];
     PolyBatchArgs a{};
     a.e.coeffs = coeffs.data();
@@ -122,7 +129,7 @@ static void poly_case(size_t ncoeffs, size_t stride, uint32_t batch, uint32_t np
     a.stride = stride;
     a.batch = batch;
     for (uint32_t p = 0; p < npoints; ++p) {
-        points[p] = p == 0 ? BB_P - 1u : p == 1 ? 1u : (uint32_t)(splitmix() % BB_P);
+        points[p] = sat ? (p == 0 ? SAT_X : BB_P - 1u) : p == 0 ? BB_P - 1u : p == 1 ? 1u : (uint32_t)(splitmix() % BB_P);
         a.e.zR[p] = to_mont_host(points[p]);
         a.e.z16R[p] = to_mont_host(bb_pow_host(points[p], POLY_PER_THREAD));
         a.e.zchunkR[p] = to_mont_host(bb_pow_host(points[p], POLY_CHUNK));
@@ -160,7 +167,14 @@ static void poly_case(size_t ncoeffs, size_t stride, uint32_t batch, uint32_t np
     std::printf("\n");
 }
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "saturated") {
+        for (uint32_t nterms : {4u, 5u, 8u, 64u, 65u})
+            for (int log_blowup : {0, 2}) deep_case(6, log_blowup, 8, nterms, 0, 0, -1, true);
+        for (size_t nc : {(size_t)17, (size_t)4097}) poly_case(nc, nc + 3, 3, 2, true);
+        std::printf("DONE\n");
+        return 0;
+    }
     const int log_Ns[] = {0, 1, 2, 3, 6, 10};
     uint32_t k = 0;
     for (int log_N : log_Ns)

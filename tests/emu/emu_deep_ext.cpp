@@ -15,12 +15,17 @@
 #include <cstdint>
 #include <cstdio>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "ntt_plan.hpp"
 #include "prover_kernels.hpp"
+#include "contract_case.hpp"
 
 using namespace toyni;
+
+// `saturated` as the only argument runs, instead of the cases above, the ones whose every product is (p - 1)^2: every data word
+// p - 1 and every weight, claim and point SAT_X, the plain value whose Montgomery form is p - 1 (same record format)
 
 static uint64_t sm_state = 0xE47DEE9ull;
 static uint64_t splitmix() {
@@ -42,7 +47,8 @@ struct Term { uint32_t column, rotation, alpha[4], value[4]; };
 
 // z_at >= 0: z is the coset's point of that index (a base-field z).  Otherwise `upper` of z's coordinates 1..3 are non-zero
 // (upper = 0: a base-field z off the coset).
-static void deep_case(int log_N, int log_blowup, uint32_t width, uint32_t nterms, uint32_t pad, uint32_t offset_words, long z_at, int upper) {
+static void deep_case(int log_N, int log_blowup, uint32_t width, uint32_t nterms, uint32_t pad, uint32_t offset_words, long z_at, int upper, bool sat = false) {
+    TOYNI_CONTRACT_TAG("deep_combine_ext_group log_N=%d width=%u nterms=%u sat=%d", log_N, width, nterms, (int)sat);
     NttPlan plan;
     if (!build_plan(log_N, plan)) { std::printf("FAIL plan\n"); return; }
     const uint64_t N = 1ull << log_N, rows = N >> log_blowup, col_stride = N + pad;
@@ -61,8 +67,8 @@ static void deep_case(int log_N, int log_blowup, uint32_t width, uint32_t nterms
         terms[t].column = (uint32_t)(splitmix() % width);
         terms[t].rotation = (t % 3 == 2) ? (uint32_t)(rows - 1) : (uint32_t)(splitmix() % rows);   // (i + rotation * B) passes N
         for (int k = 0; k < 4; ++k) {
-            terms[t].alpha[k] = draw(t + nterms + 3u * k);
-            terms[t].value[k] = draw(t + 2 * nterms + 1 + 2u * k);
+            terms[t].alpha[k] = sat ? SAT_X : draw(t + nterms + 3u * k);
+            terms[t].value[k] = sat ? SAT_X : draw(t + 2 * nterms + 1 + 2u * k);
         }
     }
     if (nterms >= 2) { terms[1].column = terms[0].column; terms[1].rotation = terms[0].rotation; }   // a repeated (column, rotation)
@@ -71,7 +77,7 @@ static void deep_case(int log_N, int log_blowup, uint32_t width, uint32_t nterms
     uint32_t* m = store + offset_words;
     for (size_t k = 0; k < words; ++k) m[k] = 0xFFFFFFF0u;   // the slack between N and col_stride: never read (>= p would show)
     for (uint32_t c = 0; c < width; ++c)
-        for (uint64_t i = 0; i < N; ++i) m[c * col_stride + i] = draw(splitmix());
+        for (uint64_t i = 0; i < N; ++i) m[c * col_stride + i] = sat ? BB_P - 1u : draw(splitmix());
 
     // what toyni_deep_combine_ext_device prepares
     std::vector<DeepExtTerm> table(nterms);
@@ -127,11 +133,12 @@ static void deep_case(int log_N, int log_blowup, uint32_t width, uint32_t nterms
     ::operator delete(store, std::align_val_t(16));
 }
 
-static void poly_case(size_t ncoeffs, size_t stride, uint32_t batch, uint32_t npoints) {
+static void poly_case(size_t ncoeffs, size_t stride, uint32_t batch, uint32_t npoints, bool sat = false) {
+    TOYNI_CONTRACT_TAG("poly_ext ncoeffs=%zu batch=%u npoints=%u sat=%d", ncoeffs, batch, npoints, (int)sat);
     std::vector<uint32_t> coeffs(batch ? (size_t)(batch - 1) * stride + ncoeffs : 0);   // exactly the words the layout owns
     for (auto& c : coeffs) c = 0xFFFFFFF0u;
     for (uint32_t b = 0; b < batch; ++b)
-        for (size_t i = 0; i < ncoeffs; ++i) coeffs[b * stride + i] = draw(splitmix());
+        for (size_t i = 0; i < ncoeffs; ++i) coeffs[b * stride + i] = sat ? BB_P - 1u : draw(splitmix());
     uint32_t points[POLY_MAX_POINTS][4];
     PolyExtArgs a{};
     a.coeffs = coeffs.data();
@@ -141,7 +148,7 @@ static void poly_case(size_t ncoeffs, size_t stride, uint32_t batch, uint32_t np
     a.npoints = npoints;
     a.nblocks = (uint32_t)((ncoeffs + POLY_CHUNK - 1) / POLY_CHUNK);
     for (uint32_t p = 0; p < npoints; ++p) {
-        for (int k = 0; k < 4; ++k) points[p][k] = p == 0 ? BB_P - 1u : p == 1 ? (k == 0 ? 1u : 0u) : p == 2 ? draw(splitmix()) : (uint32_t)(splitmix() % BB_P);
+        for (int k = 0; k < 4; ++k) points[p][k] = sat ? (p == 0 ? SAT_X : BB_P - 1u) : p == 0 ? BB_P - 1u : p == 1 ? (k == 0 ? 1u : 0u) : p == 2 ? draw(splitmix()) : (uint32_t)(splitmix() % BB_P);
         // what toyni_poly_eval_ext_batch_device prepares
         uint32_t z16[4], zchunk[4], zstride[4];
         ext_pow_host(points[p], POLY_PER_THREAD, z16);
@@ -188,7 +195,14 @@ static void poly_case(size_t ncoeffs, size_t stride, uint32_t batch, uint32_t np
     std::printf("\n");
 }
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "saturated") {
+        for (uint32_t nterms : {4u, 5u, 8u, 64u, 65u})
+            for (int log_blowup : {0, 2}) deep_case(6, log_blowup, 8, nterms, 0, 0, -1, 3, true);
+        for (size_t nc : {(size_t)17, (size_t)4097}) poly_case(nc, nc + 3, 3, 2, true);
+        std::printf("DONE\n");
+        return 0;
+    }
     const int log_Ns[] = {0, 1, 2, 3, 6, 10};
     uint32_t k = 0;
     for (int log_N : log_Ns)

@@ -7,11 +7,16 @@
 // it must not read one.
 #include <cstdint>
 #include <cstdio>
+#include <string>
 #include <vector>
 
 #include "prover_kernels.hpp"
+#include "contract_case.hpp"
 
 using namespace toyni;
+
+// `saturated` as the only argument runs, instead of the cases above, the ones whose every product is (p - 1)^2: every data word
+// p - 1 and every challenge coordinate SAT_X, the plain value whose Montgomery form is p - 1 (same record format)
 
 static const uint32_t P = BB_P;
 static uint64_t sm_state = 0x243F6A8885A308D3ull;
@@ -31,6 +36,7 @@ struct Case { Ext4 a, b; uint32_t x; uint32_t beta[4]; };
 
 template <bool SALTED>
 static void run(const Case& c) {
+    TOYNI_CONTRACT_TAG("fold_ext_commit_one salted=%d x=%u beta0=%u", (int)SALTED, c.x, c.beta[0]);
     uint8_t salt[16];
     for (auto& s : salt) s = SALTED ? (uint8_t)splitmix() : 0;
     uint32_t sw[4];
@@ -57,7 +63,18 @@ static void run(const Case& c) {
     std::printf("\n");
 }
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "saturated") {   // a - b is saturated against b = 0 (and vanishes against b = a); x^-1 = SAT_X as well
+        const Ext4 top{{P - 1u, P - 1u, P - 1u, P - 1u}}, zero{{0u, 0u, 0u, 0u}};
+        for (uint32_t x : {bb_inv_host(SAT_X), SAT_X, P - 1u, 7u})
+            for (int form = 0; form < 3; ++form) {
+                const Case c{form == 2 ? zero : top, form == 1 ? zero : top, x, {SAT_X, SAT_X, SAT_X, SAT_X}};
+                run<true>(c);
+                run<false>(c);
+            }
+        std::printf("DONE\n");
+        return 0;
+    }
     const uint32_t edge[3] = {0u, 1u, P - 1u};
     const uint32_t xs[4] = {1u, P - 1u, 7u, 0u /* random */};
     std::vector<Case> cases;

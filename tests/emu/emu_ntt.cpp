@@ -14,6 +14,7 @@
 #include "ntt_plan.hpp"
 #include "merkle_kernels.hpp"
 #include "prover_kernels.hpp"
+#include "contract_case.hpp"
 
 extern "C" {
 uint64_t orc_bb_mul(uint64_t, uint64_t);
@@ -40,6 +41,15 @@ uint64_t orc_bb_root_of_unity(uint32_t);
 }
 
 using namespace toyni;
+
+// "S" cases: 1069547521 is the plain value whose Montgomery form is p - 1, so with it as every constant and p - 1 as every data
+// word each product of a data word and a constant is (p - 1)^2
+// input patterns: 0 splitmix, 1 the reference's 7 i + 3, 2 every word p - 1, 3 alternating 0 / p - 1
+static void fill_pattern(uint64_t* v, size_t n, int pattern, uint64_t seed) {
+    if (pattern == 0) orc_fill_splitmix(v, n, seed);
+    else if (pattern == 1) orc_fill_pattern_7i3(v, n);
+    else for (size_t i = 0; i < n; ++i) v[i] = (pattern == 2 || (i & 1)) ? BB_P - 1u : 0u;
+}
 
 static int failures = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { ++failures; std::printf("FAIL %s:%d: ", __FILE__, __LINE__); std::printf(__VA_ARGS__); std::printf("\n"); } } while (0)
@@ -95,6 +105,7 @@ static void emu_transform(const NttPlan& plan, bool inverse, const uint32_t* src
     if (LQ == 0 && use_row2048 && plan.log_n == 12 && !lde_log) {   // two waves per transform: the pair steps through its row, a barrier between steps
         bool okr = row2048_transform(plan, blob.data(), inverse, src, dst, batch, [&](const PassArgs& a, uint64_t rows) {
             using R = Row4096;
+            TOYNI_CONTRACT_TAG("ntt_row4096 inverse=%d shift=%u", (int)inverse, shift);
             std::vector<uint32_t> row_lds(R::ROW_WORDS, 0xDEADBEEFu);
             std::vector<uint32_t> regs(128 * R::E);
             for (uint64_t row = 0; row < rows; ++row) {
@@ -110,6 +121,7 @@ static void emu_transform(const NttPlan& plan, bool inverse, const uint32_t* src
     if (LQ == 0 && use_row2048 && plan.log_n == 11 && !lde_log) {   // one wave per transform: stepped wave by wave, lane by lane within a step
         bool okr = row2048_transform(plan, blob.data(), inverse, src, dst, batch, [&](const PassArgs& a, uint64_t rows) {
             using R = Row2048;
+            TOYNI_CONTRACT_TAG("ntt_row2048 inverse=%d shift=%u", (int)inverse, shift);
             std::vector<uint32_t> row_lds(R::ROW_WORDS, 0xDEADBEEFu);   // exactly one wave's slice: an overrun is an ASan error
             std::vector<uint32_t> regs(64 * R::E);
             for (uint64_t row = 0; row < rows; ++row) {
@@ -131,6 +143,7 @@ static void emu_transform(const NttPlan& plan, bool inverse, const uint32_t* src
     if (LQ == 0 && use_lds && plan.lds_la && !lde_log) {      // n = 2^11 .. 2^15: the single-sweep kernel, phase by phase (two barriers)
         bool okl = lds_transform(plan, blob.data(), inverse, src, dst, batch, [&](auto pass, const LdsArgs& g, uint64_t ntiles) {
             using L = decltype(pass);
+            TOYNI_CONTRACT_TAG("ntt_lds threads=%u log_n=%d inverse=%d shift=%u", (unsigned)L::T, plan.log_n, (int)inverse, shift);
             std::vector<uint32_t> lds(L::LDS_WORDS, 0xDEADBEEFu);
             std::vector<uint32_t> regs((size_t)L::T * L::E);
             for (uint64_t tile = 0; tile < ntiles; ++tile) {
@@ -152,6 +165,7 @@ static void emu_transform(const NttPlan& plan, bool inverse, const uint32_t* src
     bool ok = for_each_pass<LQ>(knobs, plan, blob.data(), inverse, src, work, dst, batch, [&](auto pass, auto lzc, const PassArgs& a, uint64_t nblocks) {
         using P = decltype(pass);
         constexpr int LZ = decltype(lzc)::value;
+        TOYNI_CONTRACT_TAG("ntt_pass steps=%d threads=%u lz=%d lq=%d log_n=%d inverse=%d shift=%u", (int)P::STEPS, (unsigned)P::T, LZ, LQ, plan.log_n, (int)inverse, shift);
         std::vector<uint32_t> lds(P::LDS_WORDS, 0xDEADBEEFu);  // exact size: an out-of-range LDS word is an ASan error
         std::vector<char> seen(nblocks, 0);
         for (uint64_t v = 0; v < nblocks; ++v) {
@@ -162,15 +176,17 @@ static void emu_transform(const NttPlan& plan, bool inverse, const uint32_t* src
         }
     }, cs, lde_log);
     CHECK(ok, "no pass instantiation for log_n=%d", plan.log_n);
+    TOYNI_CONTRACT_TAG("(between cases)");
 }
 
 // BabyBearDomain::fft / ifft on a coset (src/math/domain.rs:85-123) with the scaling fused into the passes
-static void test_coset(int log_n, uint64_t batch, uint32_t shift) {
+static void test_coset(int log_n, uint64_t batch, uint32_t shift, int pattern = 0) {
     NttPlan plan;
     CHECK(build_plan(knobs, log_n, plan, latency_plan), "plan %d", log_n);
     const size_t n = (size_t)1 << log_n;
     std::vector<uint64_t> ref(n * batch), want(n * batch);
-    orc_fill_splitmix(ref.data(), n * batch, 0xC05E7ull + log_n);
+    if (pattern == 0) orc_fill_splitmix(ref.data(), n * batch, 0xC05E7ull + log_n);   // one stream over the batch: every vector differs
+    else for (uint64_t b = 0; b < batch; ++b) fill_pattern(ref.data() + b * n, n, pattern, 0);
     std::vector<uint32_t> in(n * batch), work(n * batch), out(n * batch);
     for (size_t i = 0; i < n * batch; ++i) in[i] = (uint32_t)ref[i];
     for (uint64_t b = 0; b < batch; ++b) orc_domain_fft(want.data() + b * n, n, ref.data() + b * n, n, shift);
@@ -257,7 +273,7 @@ static void test_ntt(int log_n, uint64_t batch, int pattern) {
     const size_t n = (size_t)1 << log_n;
     std::vector<uint64_t> ref(n * batch);
     if (pattern == 0) orc_fill_splitmix(ref.data(), n * batch, 0x70796E69ull + ((uint64_t)log_n << 32));
-    else for (uint64_t b = 0; b < batch; ++b) orc_fill_pattern_7i3(ref.data() + b * n, n);
+    else for (uint64_t b = 0; b < batch; ++b) fill_pattern(ref.data() + b * n, n, pattern, 0);
     std::vector<uint32_t> in(n * batch), work(n * batch, 0xABABABABu), out(n * batch, 0xCDCDCDCDu);
     for (size_t i = 0; i < n * batch; ++i) in[i] = (uint32_t)ref[i];
 
@@ -363,12 +379,14 @@ static void test_fold_xs_batch() {
     }
 }
 
-static void test_fold_ext(size_t len) {
+static void test_fold_ext(size_t len, bool saturated = false) {
+    TOYNI_CONTRACT_TAG("fold_ext len=%zu saturated=%d", len, (int)saturated);
     const size_t half = len / 2;
     std::vector<uint64_t> evals(4 * len), xs(len), want(4 * half);
-    orc_fill_splitmix(evals.data(), 4 * len, 4242);
+    fill_pattern(evals.data(), 4 * len, saturated ? 2 : 0, 4242);
     orc_domain_elements(xs.data(), len, 7);
-    const uint64_t beta[4] = {123456789ull, 987654321ull, 5ull, BB_P - 1ull};
+    const uint64_t sat = SAT_X;
+    const uint64_t beta[4] = {saturated ? sat : 123456789ull, saturated ? sat : 987654321ull, saturated ? sat : 5ull, saturated ? sat : BB_P - 1ull};
     orc_fri_fold_ext(want.data(), evals.data(), len, xs.data(), beta);
     uint32_t bh[4];
     for (int k = 0; k < 4; ++k) bh[k] = bb_mul_host((uint32_t)beta[k], BB_HALF);
@@ -380,7 +398,18 @@ static void test_fold_ext(size_t len) {
         const Ext4 r = fold_ext_one(a, b, to_mont_host(bb_inv_host((uint32_t)xs[i])), f);
         for (int k = 0; k < 4; ++k) if (r.c[k] != (uint32_t)want[4 * i + k]) ++bad;
     }
-    CHECK(bad == 0, "fold_ext len=%zu: %zu mismatches", len, bad);
+    if (saturated) {   // (a + b) / 2 + (a - b) ...: with a = b the difference vanishes; b = 0 keeps it saturated
+        for (size_t i = 0; i < half; ++i)
+            for (int k = 0; k < 4; ++k) evals[4 * (i + half) + k] = 0;
+        orc_fri_fold_ext(want.data(), evals.data(), len, xs.data(), beta);
+        for (size_t i = 0; i < half; ++i) {
+            Ext4 a, b;
+            for (int k = 0; k < 4; ++k) { a.c[k] = BB_P - 1u; b.c[k] = 0u; }
+            const Ext4 r = fold_ext_one(a, b, to_mont_host(bb_inv_host((uint32_t)xs[i])), f);
+            for (int k = 0; k < 4; ++k) if (r.c[k] != (uint32_t)want[4 * i + k]) ++bad;
+        }
+    }
+    CHECK(bad == 0, "fold_ext len=%zu saturated=%d: %zu mismatches", len, (int)saturated, bad);
 }
 
 // Merkle: leaf / node digests of merkle_kernels.hpp vs the oracle's byte-level tree (src/merkle.rs:25-48,105-123)
@@ -451,12 +480,12 @@ static void test_merkle_coop() {
 }
 
 // Low-degree extension: compact input (n >> lde_log words per transform), zero padding implied, coset shift fused
-static void test_lde(int log_n, uint64_t batch, int lde_log, uint32_t shift) {
+static void test_lde(int log_n, uint64_t batch, int lde_log, uint32_t shift, int pattern = 0) {
     NttPlan plan;
     CHECK(build_plan(knobs, log_n, plan, latency_plan), "plan %d", log_n);
     const uint64_t n = 1ull << log_n, n_in = n >> lde_log;
     std::vector<uint64_t> c64(n_in * batch);
-    orc_fill_splitmix(c64.data(), c64.size(), 0x1DE0000ull + (uint64_t)log_n * 64 + (uint64_t)lde_log);
+    fill_pattern(c64.data(), c64.size(), pattern, 0x1DE0000ull + (uint64_t)log_n * 64 + (uint64_t)lde_log);
     std::vector<uint32_t> in(n_in * batch), out(n * batch, 0xDEADBEEFu), work(n * batch);  // `in` is EXACTLY the compact size
     for (size_t i = 0; i < in.size(); ++i) in[i] = (uint32_t)c64[i];
     emu_transform(plan, false, in.data(), work.data(), out.data(), batch, shift, lde_log);
@@ -773,6 +802,18 @@ int main(int argc, char** argv) {
             test_ext(lg, vecs, 1234567891u);
             if (lg >= 11) { test_ext(lg, vecs, 7, 5); test_ext(lg, vecs, 7, 2); }
             std::printf("ext %s failures=%d\n", argv[i], failures);
+            std::fflush(stdout);
+            continue;
+        }
+        if (argv[i][0] == 'S') {                    // "SLOG": saturated operands -- every word p - 1, and alternating 0 / p - 1; plain, coset SAT_X, LDE by 4
+            const int lg = std::atoi(argv[i] + 1);
+            for (int pattern : {2, 3}) {
+                test_ntt(lg, 2, pattern);
+                test_coset(lg, 2, SAT_X, pattern);
+                if (lg >= 11) test_lde(lg, 2, 2, SAT_X, pattern);
+            }
+            test_fold_ext(lg >= 10 ? 1024 : (size_t)1 << lg, true);
+            std::printf("saturated %s failures=%d\n", argv[i], failures);
             std::fflush(stdout);
             continue;
         }

@@ -19,8 +19,10 @@
 #include <vector>
 
 #include "prover_kernels.hpp"
+#include "contract_case.hpp"
 
 using namespace toyni;
+
 
 constexpr int G = 4, T = 128, NW = T / (int)SCAN_WAVE, TILE = G * T;
 constexpr uint32_t SLACK = 0xFFFFFFF0u;
@@ -173,6 +175,7 @@ static void print_col(const char* tag, uint32_t b, const uint32_t* v, size_t n) 
 
 static int bad = 0;
 static void scan_case(int op, size_t n, uint32_t batch, bool has_num, bool has_den, int inplace, uint32_t off, Zeros zeros, bool edges = true) {
+    TOYNI_CONTRACT_TAG("column_scan op=%d n=%zu batch=%u num=%d den=%d inplace=%d", op, n, batch, (int)has_num, (int)has_den, inplace);
     const size_t pad_n = batch > 1 ? 3 : 0, pad_d = batch > 1 ? 5 : 0;
     const size_t ns = n + pad_n, ds = n + pad_d, os = inplace == 1 ? ns : inplace == 2 ? ds : n + (batch > 1 ? 1 : 0);
     Buf num(has_num ? (batch - 1) * ns + n : 1, off), den(has_den ? (batch - 1) * ds + n : 1, (off + 1) % 4), out((batch - 1) * os + n, (off + 2) % 4);
@@ -224,6 +227,7 @@ static void scan_case(int op, size_t n, uint32_t batch, bool has_num, bool has_d
 }
 
 static void inverse_case(size_t count, uint32_t off, bool inplace) {
+    TOYNI_CONTRACT_TAG("batch_inverse count=%zu off=%u inplace=%d", count, off, (int)inplace);
     Buf in(count, off), out(count, (off + 3) % 4);
     for (size_t i = 0; i < count; ++i) in.p[i] = draw(splitmix());
     if (count >= (size_t)2 * G) for (int j = 0; j < G; ++j) in.p[G + j] = 0;   // a whole group of zeros

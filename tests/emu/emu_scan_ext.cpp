@@ -15,11 +15,16 @@
 #include <cstdio>
 #include <cstring>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "prover_kernels.hpp"
+#include "contract_case.hpp"
 
 using namespace toyni;
+
+// `saturated` as the only argument runs, instead of the cases above, the ones whose every product is (p - 1)^2: every data word
+// p - 1 and every challenge coordinate SAT_X, the plain value whose Montgomery form is p - 1 (same record format)
 
 constexpr int G = 4, T = 128, NW = T / (int)SCAN_WAVE, TILE = G * T;
 constexpr uint32_t SLACK = 0xFFFFFFF0u;
@@ -200,7 +205,9 @@ static size_t operand_words(uint32_t width, uint32_t batch, size_t stride, size_
 
 static int bad = 0;
 // base_shift: the denominator's shift is (s, 0, 0, 0) -- the only shifts under which a width-1 denominator can vanish
-static void scan_case(int op, size_t n, uint32_t batch, uint32_t nw, uint32_t dw, int inplace, uint32_t off, Zeros zeros, bool base_shift, bool edges = true) {
+static void scan_case(int op, size_t n, uint32_t batch, uint32_t nw, uint32_t dw, int inplace, uint32_t off, Zeros zeros, bool base_shift, bool edges = true,
+                      bool sat = false) {
+    TOYNI_CONTRACT_TAG("ext_accum op=%d n=%zu batch=%u nw=%u dw=%u inplace=%d sat=%d", op, n, batch, nw, dw, inplace, (int)sat);
     const size_t pad_n = batch > 1 ? 3 : 0, pad_d = batch > 1 ? 5 : 0;
     const size_t ns = n + pad_n, ds = n + pad_d, os = inplace == 1 ? ns : inplace == 2 ? ds : n + (batch > 1 ? 1 : 0);
     Buf num(operand_words(nw, batch, ns, n), off), den(operand_words(dw, batch, ds, n), (off + 1) % 4), out(operand_words(4, batch, os, n), (off + 2) % 4);
@@ -228,11 +235,19 @@ static void scan_case(int op, size_t n, uint32_t batch, uint32_t nw, uint32_t dw
                 for (int k = 0; k < 4; ++k) den.p[(4 * b + k) * ds + i] = bb_add(d[k], neg(a.den.shift[k]));
             }
         }
+    if (sat) {   // gamma = (SAT_X, SAT_X, SAT_X, SAT_X) on both operands, every stored word p - 1
+        for (int k = 0; k < 4; ++k) a.num.shift[k] = nw ? SAT_X : 0u, a.den.shift[k] = dw ? SAT_X : 0u;
+        for (uint32_t b = 0; b < batch; ++b)
+            for (size_t i = 0; i < n; ++i) {
+                for (uint32_t k = 0; k < nw; ++k) num.p[(nw * b + k) * ns + i] = BB_P - 1u;
+                for (uint32_t k = 0; k < dw; ++k) den.p[(dw * b + k) * ds + i] = BB_P - 1u;
+            }
+    }
     ExtAccumSeeds in{};
     std::vector<uint32_t> init(4 * batch);
     for (uint32_t b = 0; b < batch; ++b)
         for (int k = 0; k < 4; ++k) {
-            init[4 * b + k] = b == 0 ? (op == (int)SCAN_PRODUCT && k == 0 ? 1u : 0u) : draw(b + 1 + n + k);
+            init[4 * b + k] = sat ? SAT_X : b == 0 ? (op == (int)SCAN_PRODUCT && k == 0 ? 1u : 0u) : draw(b + 1 + n + k);
             if (op == (int)SCAN_PRODUCT && k == 0 && init[4 * b] == 0u) init[4 * b] = BB_P - 1u;
             in.v[b][k] = op == (int)SCAN_PRODUCT ? to_mont_host(init[4 * b + k]) : init[4 * b + k];
         }
@@ -271,7 +286,8 @@ static void scan_case(int op, size_t n, uint32_t batch, uint32_t nw, uint32_t dw
     }
 }
 
-static void inverse_case(size_t count, uint32_t off, bool inplace) {
+static void inverse_case(size_t count, uint32_t off, bool inplace, bool sat = false) {
+    TOYNI_CONTRACT_TAG("ext_invert_group count=%zu off=%u sat=%d", count, off, (int)sat);
     const size_t is = count + (off % 2 ? 3 : 0), os = inplace ? is : count + 1;
     Buf in(3 * is + count, off), out(3 * os + count, (off + 3) % 4);
     for (size_t i = 0; i < count; ++i) {
@@ -279,7 +295,7 @@ static void inverse_case(size_t count, uint32_t off, bool inplace) {
         for (int k = 0; k < 4; ++k) d[k] = draw(splitmix());
         if (i % 5 == 1) d[i % 4] = d[(i + 1) % 4] = d[(i + 2) % 4] = 0u;
         if (i % 11 == 7 || (count >= (size_t)2 * G && i / G == 1)) d[0] = d[1] = d[2] = d[3] = 0u;   // zeros, and a whole group of them
-        for (int k = 0; k < 4; ++k) in.p[k * is + i] = d[k];
+        for (int k = 0; k < 4; ++k) in.p[k * is + i] = sat ? (i % 3 ? BB_P - 1u : SAT_X) : d[k];
     }
     std::printf("BINV %zu %u %d\n", count, off, (int)inplace);
     for (int k = 0; k < 4; ++k) print_col("IN", 0, k, in.p + k * is, count);
@@ -293,7 +309,19 @@ static void inverse_case(size_t count, uint32_t off, bool inplace) {
     std::printf("ZEROS %u\n", zeros);
 }
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc > 1 && std::string(argv[1]) == "saturated") {
+        for (int op : {(int)SCAN_SUM, (int)SCAN_PRODUCT})
+            for (size_t n : {(size_t)G + 1, (size_t)TILE + 1}) {
+                scan_case(op, n, 1, 4, 4, 0, 0, Z_NONE, false, true, true);
+                scan_case(op, n, 3, 1, 1, 0, 0, Z_NONE, false, true, true);
+                scan_case(op, n, 1, 4, 0, 0, 0, Z_NONE, false, true, true);
+                scan_case(op, n, 1, 0, 4, 0, 0, Z_NONE, false, true, true);
+            }
+        inverse_case((size_t)TILE + 1, 0, false, true);
+        std::printf("BAD %d\nDONE\n", bad);
+        return 0;
+    }
     const size_t sizes[] = {1, 2, 3, G - 1, G, G + 1, TILE - 1, TILE, TILE + 1, 2 * TILE + 5};
     const uint32_t widths[8][2] = {{1, 1}, {4, 4}, {1, 4}, {4, 1}, {0, 1}, {0, 4}, {1, 0}, {4, 0}};
     uint32_t k = 0;

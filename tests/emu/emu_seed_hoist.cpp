@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "ntt_plan.hpp"
+#include "contract_case.hpp"
 
 extern "C" {
 int orc_ntt_canonical(uint64_t*, size_t);
@@ -26,6 +27,7 @@ int orc_domain_fft(uint64_t*, size_t, const uint64_t*, size_t, uint64_t);
 }
 
 using namespace toyni;
+
 
 static int failures = 0;
 #define CHECK(cond, ...) do { if (!(cond)) { ++failures; std::printf("FAIL %s:%d: ", __FILE__, __LINE__); std::printf(__VA_ARGS__); std::printf("\n"); } } while (0)
@@ -112,6 +114,7 @@ static void run_passes(const Case& c, const LaunchKnobs& knobs, const NttPlan& p
 }
 
 static void run_case(const Case& c) {
+    TOYNI_CONTRACT_TAG("seed_hoist %s log_n=%d batch=%llu shift=%u inverse=%d lq=%d", c.what, c.log_n, (unsigned long long)c.batch, c.shift, (int)c.inverse, c.lq);
     LaunchKnobs knobs;          // defaults, not the environment
     knobs.p3_tiles = -1;        // the two-step shapes at every launch size
     knobs.s3_tiles = 99;

@@ -22,6 +22,7 @@
 
 #define TOYNI_KERNEL_TEXT_ONLY
 #include "toyni_hip.hip"
+#include "../emu/contract_case.hpp"
 
 alignas(16) uint32_t air_lds[1u << 16];   // the dynamic LDS of the AIR kernels (at most 160 KiB on the device)
 
@@ -56,6 +57,7 @@ static std::set<std::string> launched_now;     // kernel names launched by the c
 template <class F>
 static bool sim_launch(const char* name, const std::string& inst, dim3 grid, uint32_t block, F&& body) {
     instantiations.insert(std::string(name) + inst);
+    TOYNI_CONTRACT_TAG("%s%s", name, inst.c_str());
     launched_now.insert(name);
     const bool ok = hipsim::launch(name, inst, grid, block, body);
     if (!ok) ++failures;

@@ -18,6 +18,7 @@
 
 #define TOYNI_KERNEL_TEXT_ONLY
 #include "toyni_hip.hip"
+#include "../emu/contract_case.hpp"
 
 alignas(16) uint32_t air_lds[4];   // named by the kernel section; no kernel that uses it runs here
 
@@ -37,6 +38,7 @@ static std::set<std::string> instantiations;
 template <class F>
 static bool sim_launch(const char* name, const std::string& inst, dim3 grid, uint32_t block, F&& body) {
     instantiations.insert(std::string(name) + inst);
+    TOYNI_CONTRACT_TAG("%s%s", name, inst.c_str());
     const bool ok = hipsim::launch(name, inst, grid, block, body);
     if (!ok) ++failures;
     return ok;

@@ -5,6 +5,28 @@ import subprocess
 
 import __graft_entry__ as entry
 
+# the arguments of test_kernel_bodies_match_oracle_on_cpu (tests/test_field_contracts.py runs the contract build with the same list)
+EMU_NTT_ARGS = ["14", "16", "18", "19", "20", "20x2", "20x4", "20x16", "21", "s20x2", "s21x4", "s18x4",
+                # lLOGxZ: low-degree extension with 2^Z-fold implied zero padding -- every remaining first-pass shape
+                # ((4,4) at 2^16, (5,4) at 2^18, (5,5) at 2^20) across zero fractions, incl. blow-ups > 32
+                "l16x1", "l16x4", "l16x5", "l16x8", "l18x3", "l18x5", "l18x9", "l20x1", "l20x3", "l20x4", "l20x7", "l20x10", "l24x5",
+                # eLOGxV: V Ext vectors (AoS) through the interleaved passes -- plain, coset, LDE by 32 and by 4; 2^20 x 4 vectors reaches
+                # the 32-wide 1024-point shapes, a lone vector the 16-wide ones (sizes up to 2^14 run in the default loop)
+                "e16", "e18x2", "e20", "e20x4", "e21",
+                "p-1", "16", "18", "20", "s20x2", "l16x5", "l18x3", "l20x5", "l20x10",
+                # wN: launches of >= 2^N 32-wide tiles take the 64-wide shapes of the 128/256/512-point passes; w0 = always
+                "w0", "13", "14x3", "15", "16", "17x2", "18", "19", "21", "22", "s21x4", "s18x2", "e14x3", "e16x2", "e18",
+                # Q1: n = 2^21 / 2^22 through their two-pass latency plans (2048-point three-step shapes), plain / coset / LDE
+                "w10", "p6", "Q1", "21", "22", "l21x5", "l21x3", "l22x5", "l21x10", "l22x11",
+                # (round 5) the STREAMING 2048-point shapes of the same plans (16-wide tiles, 32 elements per thread, from 2^7 32-wide
+                # tiles' worth: four transforms of 2^21, two of 2^22): closing row pass (stepped wave by wave through steps 1 and 2 --
+                # it has no barrier there), the column pass as the first pass of an LDE in every zero fraction, coset forms
+                "21x4", "b4", "l21x5", "l21x2", "b2", "l22x5", "l22x1", "l22x2", "l22x8",
+                # and the interleaved (Ext) form of the streaming closing pass: a lone vector (already 2^7 32-wide tiles' worth),
+                # plain / coset / LDE by 32 and 4 (two vectors, and zero fractions 3 and 4 of the column shape: once by hand,
+                # `emu_ntt 0 Q1 e21x2 l22x3 l22x4`; the GPU tests cover them against the oracle)
+                "e21", "Q0"]   # (once by hand: `emu_ntt 0 Q1 e22` -- the LDE of Ext vectors to 2^22 through the interleaved 2048-point column shape, 28 s)
+
 
 def test_kernel_bodies_match_oracle_on_cpu():
     exe = entry.build_emu()
@@ -14,27 +36,7 @@ def test_kernel_bodies_match_oracle_on_cpu():
     # 2^20 over 2 (1024-point first pass, 8-wide tiles) and 2^21 over 4 (3-pass plan); 2^13, 2^14 run by default
     # pN: launches of at most 2^N 32-wide tiles run the three-step latency shapes (Pass3); the default (6) covers the single
     # transforms above, "p-1" then repeats 2^16 / 2^18 / 2^20 (and their LDE / slab forms) on the two-step shapes alone
-    res = subprocess.run([exe, "14", "16", "18", "19", "20", "20x2", "20x4", "20x16", "21", "s20x2", "s21x4", "s18x4",
-                          # lLOGxZ: low-degree extension with 2^Z-fold implied zero padding -- every remaining first-pass shape
-                          # ((4,4) at 2^16, (5,4) at 2^18, (5,5) at 2^20) across zero fractions, incl. blow-ups > 32
-                          "l16x1", "l16x4", "l16x5", "l16x8", "l18x3", "l18x5", "l18x9", "l20x1", "l20x3", "l20x4", "l20x7", "l20x10", "l24x5",
-                          # eLOGxV: V Ext vectors (AoS) through the interleaved passes -- plain, coset, LDE by 32 and by 4; 2^20 x 4 vectors reaches
-                          # the 32-wide 1024-point shapes, a lone vector the 16-wide ones (sizes up to 2^14 run in the default loop)
-                          "e16", "e18x2", "e20", "e20x4", "e21",
-                          "p-1", "16", "18", "20", "s20x2", "l16x5", "l18x3", "l20x5", "l20x10",
-                          # wN: launches of >= 2^N 32-wide tiles take the 64-wide shapes of the 128/256/512-point passes; w0 = always
-                          "w0", "13", "14x3", "15", "16", "17x2", "18", "19", "21", "22", "s21x4", "s18x2", "e14x3", "e16x2", "e18",
-                          # Q1: n = 2^21 / 2^22 through their two-pass latency plans (2048-point three-step shapes), plain / coset / LDE
-                          "w10", "p6", "Q1", "21", "22", "l21x5", "l21x3", "l22x5", "l21x10", "l22x11",
-                          # (round 5) the STREAMING 2048-point shapes of the same plans (16-wide tiles, 32 elements per thread, from 2^7 32-wide
-                          # tiles' worth: four transforms of 2^21, two of 2^22): closing row pass (stepped wave by wave through steps 1 and 2 --
-                          # it has no barrier there), the column pass as the first pass of an LDE in every zero fraction, coset forms
-                          "21x4", "b4", "l21x5", "l21x2", "b2", "l22x5", "l22x1", "l22x2", "l22x8",
-                          # and the interleaved (Ext) form of the streaming closing pass: a lone vector (already 2^7 32-wide tiles' worth),
-                          # plain / coset / LDE by 32 and 4 (two vectors, and zero fractions 3 and 4 of the column shape: once by hand,
-                          # `emu_ntt 0 Q1 e21x2 l22x3 l22x4`; the GPU tests cover them against the oracle)
-                          "e21", "Q0"],   # (once by hand: `emu_ntt 0 Q1 e22` -- the LDE of Ext vectors to 2^22 through the interleaved 2048-point column shape, 28 s)
-                         capture_output=True, text=True, timeout=1800)
+    res = subprocess.run([exe] + EMU_NTT_ARGS, capture_output=True, text=True, timeout=1800)
     assert res.returncode == 0, res.stdout[-3000:] + res.stderr[-1000:]
     assert "ALL OK" in res.stdout
     import re

@@ -65,6 +65,15 @@
 #endif
 #endif
 
+// Operand-domain hook: each primitive below names itself and its operands at its top.  Empty in every product build and in all device
+// code; a host translation unit may define it first (tests/emu/field_contracts.hpp checks the domains stated in the comments below).
+#if defined(__HIP_DEVICE_COMPILE__)
+#undef TOYNI_FIELD_CONTRACT
+#define TOYNI_FIELD_CONTRACT(prim, ...) ((void)0)
+#elif !defined(TOYNI_FIELD_CONTRACT)
+#define TOYNI_FIELD_CONTRACT(prim, ...) ((void)0)
+#endif
+
 namespace toyni {
 
 constexpr uint32_t BB_P = 2013265921u;          // src/babybear.rs:8
@@ -94,25 +103,34 @@ static_assert(BB_HALF == 1006632961u, "2^-1");
 // ---- canonical add / sub: one min() replaces compare+select ----
 // a, b in [0,p).  src/babybear.rs:129-139
 TOYNI_HD uint32_t bb_add(uint32_t a, uint32_t b) {
+    TOYNI_FIELD_CONTRACT(BB_ADD, a, b);
     uint32_t s = a + b;               // < 2p < 2^32
     uint32_t t = s - BB_P;            // wraps high when s < p
     return s < t ? s : t;
 }
 // src/babybear.rs:148-160
 TOYNI_HD uint32_t bb_sub(uint32_t a, uint32_t b) {
+    TOYNI_FIELD_CONTRACT(BB_SUB, a, b);
     uint32_t d = a - b;               // wraps high when a < b
     uint32_t t = d + BB_P;
     return d < t ? d : t;
 }
-// a - b + p in (0, 2p): congruent to a - b, valid as the left operand of mont_mul_lazy
-TOYNI_HD uint32_t bb_sub_lazy(uint32_t a, uint32_t b) { return a + (BB_P - b); }
+// a, b canonical: a - b + p in (0, 2p), congruent to a - b, valid as the left operand of mont_mul_lazy
+TOYNI_HD uint32_t bb_sub_lazy(uint32_t a, uint32_t b) {
+    TOYNI_FIELD_CONTRACT(BB_SUB_LAZY, a, b);
+    return a + (BB_P - b);
+}
 // fold [0,2p) -> [0,p)
 TOYNI_HD uint32_t bb_reduce_2p(uint32_t x) {
+    TOYNI_FIELD_CONTRACT(BB_REDUCE_2P, x);
     uint32_t t = x - BB_P;
     return x < t ? x : t;
 }
 // x / 2 mod p for canonical x
-TOYNI_HD uint32_t bb_halve(uint32_t x) { return (x >> 1) + ((x & 1u) ? BB_HALF : 0u); }
+TOYNI_HD uint32_t bb_halve(uint32_t x) {
+    TOYNI_FIELD_CONTRACT(BB_HALVE, x);
+    return (x >> 1) + ((x & 1u) ? BB_HALF : 0u);
+}
 
 // ---- Montgomery product, R = 2^32 ----
 // a: any u32, bR: Montgomery form of b with bR < p.  Returns a*b mod p up to one extra p: [0, 2p).
@@ -120,18 +138,23 @@ TOYNI_HD uint32_t bb_halve(uint32_t x) { return (x >> 1) + ((x & 1u) ? BB_HALF :
 // So a RUNNING PRODUCT of twiddles (tw <- tw * G, used only as the right-hand factor of products with canonical data and as
 // the left-hand factor of its own next step) can stay in [0, 2p): the chain skips the conditional subtract (2 of 5 instructions).
 TOYNI_HD uint32_t mont_mul_lazy(uint32_t a, uint32_t bR) {
+    TOYNI_FIELD_CONTRACT(MONT_MUL_LAZY, a, bR);
     uint64_t prod = (uint64_t)a * bR;
     uint32_t m = (uint32_t)prod * BB_NPINV;
     uint64_t t = prod + (uint64_t)m * BB_P;   // low 32 bits are zero by construction
     return (uint32_t)(t >> 32);
 }
-TOYNI_HD uint32_t mont_mul(uint32_t a, uint32_t bR) { return bb_reduce_2p(mont_mul_lazy(a, bR)); }
+TOYNI_HD uint32_t mont_mul(uint32_t a, uint32_t bR) {
+    TOYNI_FIELD_CONTRACT(MONT_MUL, a, bR);
+    return bb_reduce_2p(mont_mul_lazy(a, bR));
+}
 
 // (a - b) * w mod p as ONE Montgomery reduction of the two-term dot product a*wR + b*(p - wR):
 // a, b canonical, wR and nwR = p - wR canonical Montgomery forms (wR != 0).  The 64-bit sum stays below
 // 2 p^2, plus m*p below 2^32 p: < 2^64, quotient < 2p.  Saves the separate subtract of the butterfly
 // (integer multiply-adds issue at the add rate on gfx950, so a v_mad_u64_u32 is as cheap as a v_sub).
 TOYNI_HD uint32_t mont_dot_sub(uint32_t a, uint32_t b, uint32_t wR, uint32_t nwR) {
+    TOYNI_FIELD_CONTRACT(MONT_DOT_SUB, a, b, wR, nwR);
     uint64_t t = (uint64_t)a * wR;
     t += (uint64_t)b * nwR;
     const uint32_t m = (uint32_t)t * BB_NPINV;
@@ -140,6 +163,7 @@ TOYNI_HD uint32_t mont_dot_sub(uint32_t a, uint32_t b, uint32_t wR, uint32_t nwR
 }
 // a*bR + c*dR as one Montgomery reduction (a, c canonical; bR, dR canonical Montgomery forms): same bound as above
 TOYNI_HD uint32_t mont_dot2(uint32_t a, uint32_t bR, uint32_t c, uint32_t dR) {
+    TOYNI_FIELD_CONTRACT(MONT_DOT2, a, bR, c, dR);
     uint64_t t = (uint64_t)a * bR;
     t += (uint64_t)c * dR;
     const uint32_t m = (uint32_t)t * BB_NPINV;
@@ -151,6 +175,7 @@ TOYNI_HD uint32_t mont_dot2(uint32_t a, uint32_t bR, uint32_t c, uint32_t dR) {
 // the low word and with it m are untouched -- and then hi' 2^32 + lo + m p < 2 p 2^32 < 2^64 with a quotient below 2p.
 // Four products then cost 4 multiply-adds + 6 operations where four mont_mul + three bb_add cost 29.
 TOYNI_HD uint32_t mont_reduce_wide(uint64_t t) {
+    TOYNI_FIELD_CONTRACT(MONT_REDUCE_WIDE, t);
     const uint32_t lo = (uint32_t)t, hi = bb_reduce_2p((uint32_t)(t >> 32));
     const uint32_t m = lo * BB_NPINV;
     const uint64_t u = (((uint64_t)hi << 32) | lo) + (uint64_t)m * BB_P;

@@ -182,7 +182,10 @@ TOYNI_HD void deep_combine_group(const DeepCombineArgs& a, const DeepTerm* terms
             uint32_t v[K];
             deep_term_load<K>(a, tm, i0, v);
 #pragma unroll
-            for (int j = 0; j < K; ++j) acc[j] = (q ? acc[j] : 0ull) + (uint64_t)v[j] * tm.alphaR;
+            for (int j = 0; j < K; ++j) {
+                TOYNI_FIELD_CONTRACT(WIDE_ACC, v[j], tm.alphaR, q + 1);
+                acc[j] = (q ? acc[j] : 0ull) + (uint64_t)v[j] * tm.alphaR;
+            }
         }
 #pragma unroll
         for (int j = 0; j < K; ++j) sum[j] = bb_add(sum[j], mont_reduce_wide(acc[j]));
@@ -191,12 +194,17 @@ TOYNI_HD void deep_combine_group(const DeepCombineArgs& a, const DeepTerm* terms
         uint64_t acc[K];
 #pragma unroll
         for (int j = 0; j < K; ++j) acc[j] = 0ull;
+        const uint32_t tail0 = t;   // where the sums were zeroed: the contract hook counts the products from here
+        (void)tail0;
         for (; t < a.nterms; ++t) {
             const DeepTerm tm = deep_term_at(terms, t);
             uint32_t v[K];
             deep_term_load<K>(a, tm, i0, v);
 #pragma unroll
-            for (int j = 0; j < K; ++j) acc[j] += (uint64_t)v[j] * tm.alphaR;
+            for (int j = 0; j < K; ++j) {
+                TOYNI_FIELD_CONTRACT(WIDE_ACC, v[j], tm.alphaR, t - tail0 + 1u);
+                acc[j] += (uint64_t)v[j] * tm.alphaR;
+            }
         }
 #pragma unroll
         for (int j = 0; j < K; ++j) sum[j] = bb_add(sum[j], mont_reduce_wide(acc[j]));
@@ -358,7 +366,10 @@ TOYNI_HD void deep_combine_ext_group(const DeepExtArgs& a, const DeepExtTerm* te
 #pragma unroll
             for (int j = 0; j < K; ++j)
 #pragma unroll
-                for (int k = 0; k < 4; ++k) acc[j][k] = (q ? acc[j][k] : 0ull) + (uint64_t)v[j] * tm.alphaR[k];
+                for (int k = 0; k < 4; ++k) {
+                    TOYNI_FIELD_CONTRACT(WIDE_ACC, v[j], tm.alphaR[k], q + 1);
+                    acc[j][k] = (q ? acc[j][k] : 0ull) + (uint64_t)v[j] * tm.alphaR[k];
+                }
         }
 #pragma unroll
         for (int j = 0; j < K; ++j)
@@ -371,6 +382,8 @@ TOYNI_HD void deep_combine_ext_group(const DeepExtArgs& a, const DeepExtTerm* te
         for (int j = 0; j < K; ++j)
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[j][k] = 0ull;
+        const uint32_t tail0 = t;   // where the sums were zeroed: the contract hook counts the products from here
+        (void)tail0;
         for (; t < a.nterms; ++t) {
             const DeepExtTerm tm = deep_ext_term_at(terms, t);
             uint32_t v[K];
@@ -378,7 +391,10 @@ TOYNI_HD void deep_combine_ext_group(const DeepExtArgs& a, const DeepExtTerm* te
 #pragma unroll
             for (int j = 0; j < K; ++j)
 #pragma unroll
-                for (int k = 0; k < 4; ++k) acc[j][k] += (uint64_t)v[j] * tm.alphaR[k];
+                for (int k = 0; k < 4; ++k) {
+                    TOYNI_FIELD_CONTRACT(WIDE_ACC, v[j], tm.alphaR[k], t - tail0 + 1u);
+                    acc[j][k] += (uint64_t)v[j] * tm.alphaR[k];
+                }
         }
 #pragma unroll
         for (int j = 0; j < K; ++j)
