@@ -472,9 +472,9 @@ int toyni_column_scan_device(toyni_ntt_ctx* ctx, const uint32_t* d_num, size_t n
  *         -> toyni_poly_eval_ext_batch_device -> toyni_deep_combine_ext_device
  *         -> toyni_fri_commit_phase_ext_device (3j: every round's fold and commitment, the transcript behind a callback)
  *         -> toyni_merkle_open_rows_device(TOYNI_ROWS_ROW_MAJOR, width = 4) per layer
- *     stays on the device. The quotient under Ext weights needs nothing new: toyni_air_quotient_device is linear in its weights, so
- *     four calls with the coordinates of the weights write the quotient's four base columns, which join the DEEP combination as a
- *     second matrix (accumulate).  An Ext-valued polynomial held as four base columns q_0..q_3 (that quotient, or an Ext
+ *     stays on the device. The quotient under Ext weights is toyni_air_quotient_ext_device (3k): toyni_air_quotient_device is linear
+ *     in its weights, so four calls with the coordinates of the weights write the same four base columns, at four times the cost of
+ *     interpreting the program; the columns join the DEEP combination as a second matrix (accumulate).  An Ext-valued polynomial held as four base columns q_0..q_3 (that quotient, or an Ext
  *     accumulator of 3i) needs no entry point of its own either: evaluate the four columns here and combine on the host,
  *     q(z) = sum_j X^j q_j(z).
  *     Ext = F_p[X]/(X^4 - 11), four consecutive words c0..c3 (section 3).  Every convention is that of 3e: asynchronous on `stream`,
@@ -511,8 +511,8 @@ int toyni_deep_combine_ext_device(toyni_ntt_ctx* ctx, const uint32_t* d_values, 
  *     bits instead of 31), so that the staged AIR of 3g lives in the protocol shape of 3h.  The accumulator is then an Ext-valued
  *     column and its terms are Ext quotients.  With it the sequence for a staged AIR
  *         committed main columns -> toyni_column_scan_ext_device -> the 4 x batch base columns through the batched inverse transform,
- *         toyni_lde_device and toyni_merkle_commit_rows_device as a second matrix -> toyni_air_quotient_device under Ext weights (four
- *         calls) -> toyni_poly_eval_ext_batch_device -> toyni_deep_combine_ext_device
+ *         toyni_lde_device and toyni_merkle_commit_rows_device as a second matrix -> toyni_air_quotient_ext_device (3k: the quotient under Ext
+ *         weights) -> toyni_poly_eval_ext_batch_device -> toyni_deep_combine_ext_device
  *     stays on the device.
  *     Layout: an Ext column is FOUR base columns, one per coordinate: coordinate k of element i of Ext column b is at
  *     ptr[(4 b + k) * stride + i], stride >= n, packed-u32 canonical residues -- what four 3f calls with the coordinates of Ext weights
@@ -599,6 +599,37 @@ typedef int (*toyni_fri_ext_challenge_fn)(void* user, unsigned round, const uint
 int toyni_fri_commit_phase_ext_device(toyni_ntt_ctx* ctx, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size,
                                       const uint8_t* d_salts, toyni_fri_ext_challenge_fn challenge, void* user, uint32_t* d_layers,
                                       uint8_t* d_levels, uint8_t* h_roots, unsigned* rounds_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 3k. The quotient of 3f under Ext weights in ONE call: the last step of the protocol shape of 3h / 3i that was spelled as a
+ *     workaround (four calls of toyni_air_quotient_device, one per coordinate of the weights).  The programs, the matrices, the coset
+ *     and the TOYNI_AIR_* instruction set are those of 3f, unchanged: toyni_air_program_check / _create serve both calls, and a
+ *     program's constraint values stay in the base field.  Only the weights of the Fiat-Shamir challenge are Ext:
+ *         C_i = sum_{EMIT k, b = 0} W_k * value_k(i)                                   in Ext = F_p[X]/(X^4 - 11)
+ *         Q_i = C_i / Z_H(x_i) + sum_{EMIT k, b = 1} W_k * value_k(i)
+ *     weights4: host array of nweights Ext weights, plain canonical residues, coordinate e of weight k at weights4[4 k + e]; reusable
+ *     as soon as the call returns.  For constraints written with emit_ext (base constraint 4 k + j = coordinate j of Ext constraint k)
+ *     under Ext challenges alpha_k, W_{4 k + j} = alpha_k * X^j.
+ *     Outputs: four base columns each, column-major -- coordinate e of Q_i at d_q_out[e * out_stride + i], of C_i at
+ *     d_c_out[e * out_stride + i] (d_c_out may be NULL), out_stride >= N: the layout of 3i, which
+ *     toyni_merkle_commit_rows_device(TOYNI_ROWS_COLUMN_MAJOR, 4), the batched inverse coset transform,
+ *     toyni_poly_eval_ext_batch_device and toyni_deep_combine_ext_device read as it lies.  The words N .. out_stride of a column are
+ *     never touched.  accumulate != 0 adds into every column, as in 3f.
+ *     By definition column e is, word for word, what toyni_air_quotient_device writes under the base weights weights4[4 k + e]: the
+ *     arithmetic is exact, so the four calls and this one agree in every byte.  What differs is the cost: the program is decoded, its
+ *     cells are loaded and its register file is walked once per point instead of four times; an EMIT costs four products per point.
+ *     Refused before anything is enqueued, the outputs untouched: every refusal of toyni_air_quotient_device (with weights4 for
+ *     weights, "a weight >= p" read per coordinate), and TOYNI_E_RANGE for out_stride < N.
+ *     The launch shape, the LDS register file and the 1 / Z_H classes are those of 3f.  Each output column is written by 16-byte stores
+ *     where that column's own first word is 16-byte aligned (with an out_stride that is no multiple of 4 the columns differ), by word
+ *     stores otherwise; the result is the same.  Up to TOYNI_AIR_EXT_INLINE_WEIGHTS Ext weights (1 KiB) travel inside the kernel's
+ *     arguments, and such a call can be captured into a HIP graph; more go through the context's pinned staging ring and per-stream
+ *     buffer exactly as in 3f (the call stays asynchronous; it cannot be captured).
+ * ---------------------------------------------------------------------------------------------- */
+#define TOYNI_AIR_EXT_INLINE_WEIGHTS 64
+int toyni_air_quotient_ext_device(toyni_ntt_ctx* ctx, const toyni_air_program* prog, const toyni_air_matrix* mats, size_t nmats,
+                                  unsigned log_blowup, uint32_t shift, const uint32_t* weights4, size_t nweights,
+                                  uint32_t* d_c_out, uint32_t* d_q_out, size_t out_stride, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:

@@ -17,5 +17,6 @@ from .merkle import (MerkleTree, RowMerkleTree, ROWS_COLUMN_MAJOR, ROWS_ROW_MAJO
                      merkle_commit_rows_device, merkle_open_rows_device)
 from . import prover  # noqa: F401
 from .prover import AirBuilder, AirProgram, air_insns, air_quotient_device  # noqa: F401  (include/toyni_hip.h 3f)
+from .prover import air_ext_weights, air_quotient_ext_device  # noqa: F401  (include/toyni_hip.h 3k)
 
 P = 2013265921

@@ -125,6 +125,9 @@ SIGNATURES = {
     "toyni_air_program_info": (c_int, [c_void_p, c_void_p]),
     "toyni_air_quotient_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, ctypes.c_uint, c_u32, c_void_p, c_size, c_void_p, c_void_p, c_int,
                                           c_void_p]),
+    # section 3k
+    "toyni_air_quotient_ext_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, ctypes.c_uint, c_u32, c_void_p, c_size, c_void_p, c_void_p, c_size,
+                                              c_int, c_void_p]),
     # section 3g
     "toyni_column_scan_tile": (c_size, []),
     "toyni_batch_inverse_device": (c_int, [c_void_p, c_void_p, c_size, c_void_p, c_void_p]),

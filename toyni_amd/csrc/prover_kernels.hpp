@@ -588,6 +588,107 @@ TOYNI_HD void air_eval_group(const AirArgs& a, const uint32_t* weights, uint32_t
     for (int j = 0; j < K; ++j) q[j] = a.divides ? bb_add(mont_mul(c[j], zhR[j]), undiv[j]) : undiv[j];
 }
 
+// ---- the same programs under Ext weights (include/toyni_hip.h 3k) ----
+//   C_i = sum_{EMIT k, b = 0} W_k value_k(i),   Q_i = C_i / Z_H(x_i) + sum_{EMIT k, b = 1} W_k value_k(i),   W_k in Ext, values in F_p
+// A base value times an Ext weight is four base products, so coordinate e of the result is air_eval_group's word under the base
+// weights weights4[4 k + e]: ONE interpretation of the program with four accumulators, where four calls of the base kernel decode
+// every instruction, load every cell and walk the LDS register file four times.  Everything but EMIT and the closing step is
+// air_eval_group's text (the base function is left alone so that the base kernels' code objects stay what they are).  An EMIT loads
+// the value group once and multiplies it by the four coordinates (plain, in scalar registers): mont_mul of a plain canonical weight
+// and a canonical Montgomery value is a plain canonical product, bb_add keeps the accumulators canonical -- the operand domains of
+// bb_field.hpp hold at every step, whatever the number and order of the EMITs.
+constexpr uint32_t AIR_EXT_INLINE_WEIGHTS = 64;   // Ext weights inside the kernel arguments: 1 KiB (TOYNI_AIR_EXT_INLINE_WEIGHTS)
+template <int K>
+TOYNI_HD void air_eval_group_ext(const AirArgs& a, const uint32_t* weights4, uint32_t* regs, uint32_t stride, uint64_t i0, const uint32_t (&zhR)[K],
+                                 uint32_t (&c)[4][K], uint32_t (&q)[4][K]) {
+    uint32_t xR[K];
+    xR[0] = domain_point_mont(a.dom, i0);
+#pragma unroll
+    for (int j = 1; j < K; ++j) xR[j] = mont_mul(xR[j - 1], a.wNR);
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+#pragma unroll
+        for (int j = 0; j < K; ++j) c[e][j] = q[e][j] = 0u;   // q gathers the undivided constraints until the closing step
+    for (uint32_t pc = 0; pc < a.ninsns; ++pc) {
+        const uint32_t w0 = TOYNI_UNIFORM_LOAD(&a.insns[pc].w0), imm = TOYNI_UNIFORM_LOAD(&a.insns[pc].imm);   // the same in every lane
+        const uint32_t op = w0 & 255u, dst = (w0 >> 8) & 255u, ra = (w0 >> 16) & 255u, rb = w0 >> 24;
+        uint32_t v[K];
+        if (op == AIR_OP_EMIT) {
+            uint32_t wt[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) wt[e] = TOYNI_UNIFORM(weights4[4u * imm + e]);
+            air_reg_load<K>(regs, stride, ra, v);
+            if (rb) {   // rb is uniform: two branches, not two sums and a select
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int j = 0; j < K; ++j) q[e][j] = bb_add(q[e][j], mont_mul(wt[e], v[j]));
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int j = 0; j < K; ++j) c[e][j] = bb_add(c[e][j], mont_mul(wt[e], v[j]));
+            }
+            continue;
+        }
+        if (op >= AIR_OP_ADD) {
+            uint32_t u[K], w[K];
+            air_reg_load<K>(regs, stride, ra, u);
+            air_reg_load<K>(regs, stride, rb, w);
+            if (op == AIR_OP_MUL) {
+#pragma unroll
+                for (int j = 0; j < K; ++j) v[j] = mont_mul(u[j], w[j]);
+            } else if (op == AIR_OP_ADD) {
+#pragma unroll
+                for (int j = 0; j < K; ++j) v[j] = bb_add(u[j], w[j]);
+            } else {
+#pragma unroll
+                for (int j = 0; j < K; ++j) v[j] = bb_sub(u[j], w[j]);
+            }
+        } else if (op == AIR_OP_CELL) {
+            air_cell_load<K>(a, rb, imm, ra, i0, v);
+#pragma unroll
+            for (int j = 0; j < K; ++j) v[j] = to_mont(v[j]);
+        } else if (op == AIR_OP_XINV) {
+            deep_point_inverses<K>(a.dom, a.wNR, imm, i0, v);
+        } else {
+#pragma unroll
+            for (int j = 0; j < K; ++j) v[j] = op == AIR_OP_X ? xR[j] : imm;
+        }
+        air_reg_store<K>(regs, stride, dst, v);
+    }
+    if (a.divides) {   // four products with 1 / Z_H per point
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+#pragma unroll
+            for (int j = 0; j < K; ++j) q[e][j] = bb_add(mont_mul(c[e][j], zhR[j]), q[e][j]);
+    }
+}
+// The K words of the points i0 .. i0 + K - 1 into the four coordinate columns out + e * out_stride (out may be null: nothing is
+// written).  Whether a column takes the 16-byte store (and load, when accumulating) is decided from that column's OWN first word:
+// with an out_stride that is no multiple of 4 the columns 1..3 are not aligned even where the base pointer is.
+template <int K>
+TOYNI_HD void air_ext_store(uint32_t* out, uint64_t out_stride, uint64_t i0, uint32_t accumulate, const uint32_t (&v)[4][K]) {
+    if (!out) return;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        uint32_t* col = out + (uint64_t)e * out_stride;
+        if (K == 4 && !((uintptr_t)col & 15)) {
+            DeepQuad* d4 = reinterpret_cast<DeepQuad*>(col + i0);
+            DeepQuad r = DeepQuad{v[e][0], v[e][1 % K], v[e][2 % K], v[e][3 % K]};
+            if (accumulate) {
+                const DeepQuad p = *d4;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) r[j] = bb_add(p[j], r[j]);
+            }
+            *d4 = r;
+        } else {
+#pragma unroll
+            for (int j = 0; j < K; ++j) col[i0 + j] = accumulate ? bb_add(col[i0 + j], v[e][j]) : v[e][j];
+        }
+    }
+}
+
 // ---- accumulator columns: a running sum or product along a column (include/toyni_hip.h 3g) ----
 //   term_i = num_i / den_i (0 where den_i = 0),  out[0] = init,  out[i] = out[i-1] o term_{i-1},  o = + or *
 // The only dependency from row to row in this library.  + and * mod p are associative and commutative, so the column is cut into

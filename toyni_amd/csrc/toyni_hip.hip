@@ -914,6 +914,53 @@ __global__ void __launch_bounds__(256) air_quotient_kernel(const AirArgs a, cons
 struct AirInlineWeights { uint32_t w[AIR_INLINE_WEIGHTS]; };
 __global__ void __launch_bounds__(256) air_quotient_inline_kernel(const AirArgs a, const AirInlineWeights in) { air_quotient_body(a, in.w); }
 
+// The same programs under Ext weights (include/toyni_hip.h 3k): the launch shape, the LDS layout and the 1 / Z_H classes of
+// air_quotient_body, one interpretation per point with four accumulators (air_eval_group_ext), four coordinate columns out.
+// a.c_out / a.q_out are the first of four columns each, out_stride words apart.
+__device__ __forceinline__ void air_quotient_ext_body(const AirArgs& a, uint64_t out_stride, const uint32_t* weights4) {
+    constexpr int K = 4;
+    const uint32_t B = 1u << a.log_blowup;
+    uint32_t* zh_lds = air_lds + a.nregs * blockDim.x * K;
+    if (a.zh_lds) {
+        for (uint32_t t = threadIdx.x; t < B; t += blockDim.x) zh_lds[t] = zh_inv_class(a.shift_nR, a.wBR, t);
+        __syncthreads();
+    }
+    const uint64_t N = (uint64_t)1 << a.log_N;
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a.log_N >= 2) {
+        if (g >= N / K) return;
+        const uint64_t i0 = g * K;
+        uint32_t zhR[K], c[4][K], q[4][K];
+        if (a.zh_lds) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) zhR[j] = zh_lds[(i0 + j) & (B - 1)];
+        } else if (a.divides) {
+            air_zh_inverses<K>(a, i0, zhR);
+        } else {
+#pragma unroll
+            for (int j = 0; j < K; ++j) zhR[j] = 0u;
+        }
+        air_eval_group_ext<K>(a, weights4, air_lds + threadIdx.x * K, blockDim.x * K, i0, zhR, c, q);
+        air_ext_store<K>(a.c_out, out_stride, i0, a.accumulate, c);
+        air_ext_store<K>(a.q_out, out_stride, i0, a.accumulate, q);
+    } else if (g < N) {
+        uint32_t zhR[1] = {0u}, c[4][1], q[4][1];
+        if (a.zh_lds) zhR[0] = zh_lds[g & (B - 1)];
+        else if (a.divides) air_zh_inverses<1>(a, g, zhR);
+        air_eval_group_ext<1>(a, weights4, air_lds + threadIdx.x, blockDim.x, g, zhR, c, q);
+        air_ext_store<1>(a.c_out, out_stride, g, a.accumulate, c);
+        air_ext_store<1>(a.q_out, out_stride, g, a.accumulate, q);
+    }
+}
+__global__ void __launch_bounds__(256) air_quotient_ext_kernel(const AirArgs a, const uint64_t out_stride, const uint32_t* __restrict__ weights4) {
+    air_quotient_ext_body(a, out_stride, weights4);
+}
+// up to AIR_EXT_INLINE_WEIGHTS Ext weights inside the kernel arguments
+struct AirExtInlineWeights { uint32_t w[4 * AIR_EXT_INLINE_WEIGHTS]; };
+__global__ void __launch_bounds__(256) air_quotient_ext_inline_kernel(const AirArgs a, const uint64_t out_stride, const AirExtInlineWeights in) {
+    air_quotient_ext_body(a, out_stride, in.w);
+}
+
 // Accumulator columns (prover_kernels.hpp, include/toyni_hip.h 3g).  Every workgroup is SCAN_THREADS threads, every thread owns
 // SCAN_GROUP consecutive elements.  The workgroup-wide scan: thread-serial over the group (the caller), log2(64) cross-lane steps
 // inside each wave, the waves' totals through LDS.  Every thread of the workgroup reaches both barriers.
@@ -3831,10 +3878,10 @@ int toyni_air_program_info(const toyni_air_program* p, toyni_air_info* info) {
     return TOYNI_OK;
 }
 
-int toyni_air_quotient_device(toyni_ntt_ctx* c, const toyni_air_program* prog, const toyni_air_matrix* mats, size_t nmats, unsigned log_blowup,
-                              uint32_t shift, const uint32_t* weights, size_t nweights, uint32_t* d_c_out, uint32_t* d_q_out, int accumulate,
-                              void* stream) {
-    if (!c || !prog || !weights || !d_q_out || (!mats && nmats)) return TOYNI_E_NULL;
+// What both quotient entries (3f, 3k) refuse on the program, the matrices, the coset and the pointers, in 3f's order; the weights'
+// values are the caller's to check next, Z_H after them (air_quotient_args)
+static int air_quotient_check(const toyni_ntt_ctx* c, const toyni_air_program* prog, const toyni_air_matrix* mats, size_t nmats, unsigned log_blowup,
+                              uint32_t shift, size_t nweights, const uint32_t* d_c_out, const uint32_t* d_q_out) {
     const toyni_air_info& info = prog->info;
     const int log_N = c->plan.log_n;
     const uint64_t N = 1ull << log_N;
@@ -3846,16 +3893,19 @@ int toyni_air_quotient_device(toyni_ntt_ctx* c, const toyni_air_program* prog, c
         if (info.min_width[m] && (!mats[m].d_values || ((uintptr_t)mats[m].d_values & 3) || mats[m].width < info.min_width[m] || mats[m].width > 65536 ||
                                   mats[m].col_stride < N))
             return TOYNI_E_RANGE;
-    for (size_t k = 0; k < nweights; ++k)
-        if (weights[k] >= BB_P) return TOYNI_E_RANGE;
+    return TOYNI_OK;
+}
+// the kernel arguments and the launch shape of a call that passed air_quotient_check; TOYNI_E_ZERO_INVERSE where Z_H vanishes on the coset
+static int air_quotient_args(toyni_ntt_ctx* c, const toyni_air_program* prog, const toyni_air_matrix* mats, unsigned log_blowup, uint32_t shift,
+                             uint32_t* d_c_out, uint32_t* d_q_out, int accumulate, AirArgs& a, AirLaunchShape& shape, dim3& grid) {
+    const toyni_air_info& info = prog->info;
+    const int log_N = c->plan.log_n;
+    const uint64_t N = 1ull << log_N;
     const uint64_t n = N >> log_blowup;
     const uint32_t shift_n = bb_pow_host(shift, n);
     // Z_H(x) = 0 on the coset only if shift^n is a B-th root of unity (toyni_fib_quotient_device)
     if (info.divides_by_zh && bb_pow_host(shift_n, 1ull << log_blowup) == 1u) return TOYNI_E_ZERO_INVERSE;
-    TOYNI_CTX_LOCK(c);
-    DeviceGuard guard(c->device);
-    hipStream_t s = (hipStream_t)stream;
-    AirArgs a{};
+    a = AirArgs{};
     a.insns = prog->d_insns;
     for (uint32_t m = 0; m < info.nmatrices; ++m) {
         a.mat[m] = info.min_width[m] ? mats[m].d_values : nullptr;
@@ -3873,12 +3923,29 @@ int toyni_air_quotient_device(toyni_ntt_ctx* c, const toyni_air_program* prog, c
     a.wBR = to_mont_host(bb_pow_host(bb_root_of_unity_host((uint32_t)log_N), n));
     a.divides = info.divides_by_zh;
     a.accumulate = accumulate ? 1u : 0u;
-    const AirLaunchShape shape = air_launch_shape(info.nregs, info.divides_by_zh, log_blowup);   // prover_kernels.hpp
-    const unsigned threads = shape.threads;
-    const size_t lds = shape.lds_bytes;
+    shape = air_launch_shape(info.nregs, info.divides_by_zh, log_blowup);   // prover_kernels.hpp
     a.zh_lds = shape.zh_lds;
     const uint64_t items = log_N >= 2 ? N / 4 : N;
-    const dim3 grid((unsigned)((items + threads - 1) / threads));
+    grid = dim3((unsigned)((items + shape.threads - 1) / shape.threads));
+    return TOYNI_OK;
+}
+
+int toyni_air_quotient_device(toyni_ntt_ctx* c, const toyni_air_program* prog, const toyni_air_matrix* mats, size_t nmats, unsigned log_blowup,
+                              uint32_t shift, const uint32_t* weights, size_t nweights, uint32_t* d_c_out, uint32_t* d_q_out, int accumulate,
+                              void* stream) {
+    if (!c || !prog || !weights || !d_q_out || (!mats && nmats)) return TOYNI_E_NULL;
+    if (int rc = air_quotient_check(c, prog, mats, nmats, log_blowup, shift, nweights, d_c_out, d_q_out)) return rc;
+    for (size_t k = 0; k < nweights; ++k)
+        if (weights[k] >= BB_P) return TOYNI_E_RANGE;
+    AirArgs a;
+    AirLaunchShape shape;
+    dim3 grid;
+    if (int rc = air_quotient_args(c, prog, mats, log_blowup, shift, d_c_out, d_q_out, accumulate, a, shape, grid)) return rc;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned threads = shape.threads;
+    const size_t lds = shape.lds_bytes;
     if (nweights <= AIR_INLINE_WEIGHTS) {   // the weights ride in the kernel arguments
         AirInlineWeights in{};
         std::copy(weights, weights + nweights, in.w);
@@ -3894,6 +3961,42 @@ int toyni_air_quotient_device(toyni_ntt_ctx* c, const toyni_air_program* prog, c
     std::memcpy(h, weights, nweights * sizeof(uint32_t));
     HIPCHK(hipMemcpyAsync(sc.d_lde32, h, nweights * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(air_quotient_kernel, grid, dim3(threads), lds, s, a, sc.d_lde32);
+    return (int)hipGetLastError();
+}
+
+// ---- section 3k: the same programs under Ext weights, one interpretation per point ----
+int toyni_air_quotient_ext_device(toyni_ntt_ctx* c, const toyni_air_program* prog, const toyni_air_matrix* mats, size_t nmats, unsigned log_blowup,
+                                  uint32_t shift, const uint32_t* weights4, size_t nweights, uint32_t* d_c_out, uint32_t* d_q_out, size_t out_stride,
+                                  int accumulate, void* stream) {
+    if (!c || !prog || !weights4 || !d_q_out || (!mats && nmats)) return TOYNI_E_NULL;
+    if (int rc = air_quotient_check(c, prog, mats, nmats, log_blowup, shift, nweights, d_c_out, d_q_out)) return rc;
+    if (out_stride < ((size_t)1 << c->plan.log_n)) return TOYNI_E_RANGE;
+    for (size_t k = 0; k < 4 * nweights; ++k)
+        if (weights4[k] >= BB_P) return TOYNI_E_RANGE;
+    AirArgs a;
+    AirLaunchShape shape;
+    dim3 grid;
+    if (int rc = air_quotient_args(c, prog, mats, log_blowup, shift, d_c_out, d_q_out, accumulate, a, shape, grid)) return rc;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const uint64_t stride = out_stride;
+    if (nweights <= AIR_EXT_INLINE_WEIGHTS) {   // the weights ride in the kernel arguments
+        AirExtInlineWeights in{};
+        std::copy(weights4, weights4 + 4 * nweights, in.w);
+        hipLaunchKernelGGL(air_quotient_ext_inline_kernel, grid, dim3(shape.threads), (size_t)shape.lds_bytes, s, a, stride, in);
+        return (int)hipGetLastError();
+    }
+    // more weights: pinned staging ring -> the stream's intermediate buffer, as toyni_air_quotient_device
+    const size_t words = 4 * nweights;
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words, words, sizeof(uint32_t));
+    if (rc) return rc;
+    void* h = nullptr;
+    if ((rc = ring_slice(sc, s, words * sizeof(uint32_t), &h))) return rc;
+    std::memcpy(h, weights4, words * sizeof(uint32_t));
+    HIPCHK(hipMemcpyAsync(sc.d_lde32, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(air_quotient_ext_kernel, grid, dim3(shape.threads), (size_t)shape.lds_bytes, s, a, stride, (const uint32_t*)sc.d_lde32);
     return (int)hipGetLastError();
 }
 

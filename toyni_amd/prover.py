@@ -223,6 +223,38 @@ def air_quotient_device(ctx, prog, mats, log_blowup: int, shift: int, weights, d
                                         d_c_out or None, d_q_out, 1 if accumulate else 0, stream or None), "GPU constraint program failed")
 
 
+AIR_EXT_INLINE_WEIGHTS = 64   # TOYNI_AIR_EXT_INLINE_WEIGHTS: up to this many Ext weights ride in the kernel arguments (capturable)
+
+
+def air_quotient_ext_device(ctx, prog, mats, log_blowup: int, shift: int, weights4, d_q_out: int, out_stride: int, d_c_out: int = 0,
+                            accumulate: bool = False, stream=None) -> None:
+    """The program under Ext weights in one call (include/toyni_hip.h 3k): coordinate e of Q_i = C_i / Z_H + the undivided constraints
+    goes to d_q_out[e * out_stride + i], of C_i to d_c_out likewise; (+)= with accumulate.  weights4: one Ext weight (four canonical
+    residues) per constraint number, as rows or flat; air_ext_weights builds it from the challenges of emit_ext constraints."""
+    m = (AirMatrix * len(mats))(*[AirMatrix(d or None, w, cs) for d, w, cs in mats])
+    w = np.ascontiguousarray(weights4, dtype=np.uint32).reshape(-1)
+    if w.size % 4:
+        raise ValueError("weights4 holds four words per Ext weight")
+    check(lib.toyni_air_quotient_ext_device(ctx.handle, prog.handle, m if len(mats) else None, len(mats), log_blowup, shift, w.ctypes.data, w.size // 4,
+                                            d_c_out or None, d_q_out, out_stride, 1 if accumulate else 0, stream or None),
+          "GPU constraint program under Ext weights failed")
+
+
+def air_ext_weights(alphas):
+    """The weight table of air_quotient_ext_device for constraints written with AirBuilder.emit_ext: base constraint 4 k + j is
+    coordinate j of Ext constraint k, so it carries alphas[k] * X^j in F_p[X]/(X^4 - 11) -- a shift of the coordinates by j, those that
+    wrap past X^3 times 11.  alphas: one Ext challenge (four canonical residues) per Ext constraint.  -> (4 len(alphas), 4) uint32."""
+    out = np.zeros((4 * len(alphas), 4), dtype=np.uint32)
+    for k, alpha in enumerate(alphas):
+        a = [int(c) % _P for c in alpha]
+        if len(a) != 4:
+            raise ValueError("an Ext challenge has four coordinates")
+        for j in range(4):
+            for e in range(4):                       # X^j * a_e X^e = a_e X^(e + j),  X^4 = 11
+                out[4 * k + j, (e + j) % 4] = a[e] * 11 % _P if e + j >= 4 else a[e]
+    return out
+
+
 class AirExpr:
     """A node of AirBuilder's expression graph: key = (op, operand nodes or fields...)."""
 
