@@ -632,6 +632,65 @@ int toyni_air_quotient_ext_device(toyni_ntt_ctx* ctx, const toyni_air_program* p
                                   uint32_t* d_c_out, uint32_t* d_q_out, size_t out_stride, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * 3l. The Fiat-Shamir transcript in device memory, and the FRI commit phase on it: FiatShamirTranscript (src/transcript.rs) as a
+ *     plain struct that kernels absorb into and squeeze from, so that a round's root never has to reach the host before the next
+ *     beta exists.  The commit phases of 3c / 3j block on every round (a polled word, a host callback, a launch into an empty
+ *     queue); the phases here are asynchronous, take no callback and can be captured into a HIP graph (caveat of section 4), and the
+ *     path from the DEEP codeword to the opening records becomes stream-ordered: enqueue everything, synchronise once.
+ *     The state has a public layout.  A caller initialises it with toyni_memcpy_h2d_async of a host copy (len = the bytes absorbed so
+ *     far, status = 0, reserved = 0; the reference's transcript starts as the 14 bytes "toyni-stark-v1"); there is no init call.
+ *     d_tr is device memory, 16-byte aligned.
+ *     What the host cannot see -- it never reads len -- is reported through `status`, which is sticky and which the caller reads
+ *     after its next synchronisation: an absorb that would pass TOYNI_TRANSCRIPT_CAPACITY leaves the state as it is and stores
+ *     TOYNI_E_RANGE there; every operation on a transcript whose status is not 0 leaves the transcript unchanged and writes ZEROS to
+ *     its outputs.  (A len beyond the capacity, which only a caller's own copy can produce, is treated the same way.)
+ *     All calls are asynchronous on `stream`; each of the four helpers is one small launch (the chains are serial by definition: one
+ *     wave).  Refused on the host before anything is enqueued, the outputs untouched: TOYNI_E_NULL for a null pointer (d_bytes with
+ *     len == 0 may be null); TOYNI_E_RANGE for a d_tr that is not 16-byte aligned, a word array that is not 4-byte aligned, and what
+ *     each call lists.
+ * ---------------------------------------------------------------------------------------------- */
+#define TOYNI_TRANSCRIPT_CAPACITY 1008
+typedef struct { uint32_t len, status, reserved[2]; uint8_t bytes[TOYNI_TRANSCRIPT_CAPACITY]; } toyni_transcript;  /* 1024 B, device, 16-byte aligned */
+/* absorb (src/transcript.rs:19-21): appends `len` device-resident bytes -- a root at the end of a d_levels, out-of-domain values.
+ * TOYNI_E_RANGE for len > TOYNI_TRANSCRIPT_CAPACITY; len == 0 enqueues nothing. */
+int toyni_transcript_absorb_device(toyni_transcript* d_tr, const uint8_t* d_bytes, size_t len, void* stream);
+/* squeeze_challenge (:34-40) `count` times: h = SHA256(state), state = h, d_out[k] = (the first 8 bytes of h as a little-endian u64)
+ * mod p.  An Ext challenge (:43-50) is count = 4.  TOYNI_E_RANGE for count > 65536; count == 0 enqueues nothing. */
+int toyni_transcript_squeeze_device(toyni_transcript* d_tr, uint32_t* d_out, size_t count, void* stream);
+/* squeeze_indices(count, max) (:58-72): the same chain with the value taken mod max; a repeated value is dropped, the others are
+ * written in order of first appearance.  TOYNI_E_RANGE for count == 0, count > 256, max == 0 or count > max.  The loop is bounded at
+ * 64 count + 64 hashes, after which it sets `status` as above (for count <= max unreachable in practice: no input can make the kernel
+ * spin). */
+int toyni_transcript_squeeze_indices_device(toyni_transcript* d_tr, size_t count, uint32_t max, uint32_t* d_out, void* stream);
+/* The positions the queries open in every layer but the final one (src/fibonacci.rs:268-283): layer k = 0 .. rounds - 1 has
+ * m_k = m0 >> k elements (rounds = log2(m0 / final_size)) and gets 2 count positions, [i mod (m_k / 2), i mod (m_k / 2) + m_k / 2] per
+ * query i = d_indices[q]; the layers' lists lie back to back in d_out (rounds x 2 count words).  Each list feeds
+ * toyni_merkle_open_groups_device / toyni_merkle_open_rows_device as it lies.  TOYNI_E_RANGE for an m0 or final_size that is not a
+ * power of two, m0 > 2^32, or count > 65536; count == 0 or m0 <= final_size writes nothing. */
+int toyni_fri_query_positions_device(const uint32_t* d_indices, size_t count, size_t m0, size_t final_size, uint32_t* d_out, void* stream);
+/* The commit phases of 3c (base field) and 3j (Ext) on a device transcript.  Per round: squeeze beta from d_tr (one squeeze; four for
+ * the Ext call), fold and commit the folded layer exactly as toyni_fri_fold_commit_device / _ext_device do, absorb the 32-byte root --
+ * the operation sequence of the callback phases, where the callback absorbs the previous root and then squeezes and a last call
+ * absorbs the last root.  As there, the caller absorbs layer 0's root first (src/fibonacci.rs:205-245).
+ * d_layer0, m0, x0, final_size, d_salts, d_layers, d_levels, the alignment rules and the size refusals are those of the callback
+ * call with the same element type.  d_betas (may be NULL) receives the plain canonical beta of every round: `rounds` words, 4 rounds
+ * for the Ext call.  After the call d_tr is what the host transcript would be: toyni_transcript_squeeze_indices_device continues
+ * from it.  m0 <= final_size enqueues nothing and leaves d_tr untouched.  A d_tr whose status is set gives beta = 0 in every round;
+ * the layers and trees are still written.
+ * No host in the loop: no callback, no pinned word, no download, and the context is locked for the enqueue only.  On a warm context
+ * (one earlier call on this stream: the per-stream record buffer exists) the call enqueues one linear chain of kernels.  beta reaches
+ * a fold through a small record in that buffer, written by the one-wave kernel behind each tree in the form the fold consumes (the
+ * Montgomery form of beta / (2 x_k); the factor tables of beta / 2 for Ext).  From the first round whose folded layer has at most
+ * 2^TOYNI_FRI_TAIL_LOG leaves (environment, read once; default 9 = 512 leaves, the most one workgroup holds; -1 = never) one
+ * workgroup runs ALL remaining rounds in one launch, layer, tree level and transcript in LDS; both settings write the same bytes. */
+int toyni_fri_commit_phase_transcript_device(toyni_ntt_ctx* ctx, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size,
+                                             const uint8_t* d_salts, toyni_transcript* d_tr, uint32_t* d_layers, uint8_t* d_levels,
+                                             uint32_t* d_betas, void* stream);
+int toyni_fri_commit_phase_transcript_ext_device(toyni_ntt_ctx* ctx, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size,
+                                                 const uint8_t* d_salts, toyni_transcript* d_tr, uint32_t* d_layers, uint8_t* d_levels,
+                                                 uint32_t* d_betas, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:
  *     src/fibonacci.rs:133-150,186-198,222-245, src/math/polynomial.rs:134-144, src/merkle.rs:50-80).  All asynchronous on
  *     `stream`; packed u32 device data; ctx = a context of size N = the LDE size (its domain table supplies x_i = shift w_N^i).

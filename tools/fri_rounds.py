@@ -8,7 +8,16 @@ toyni_merkle_commit_rows_device(width 4, row-major), toyni_stream_synchronize an
 round of each at m = 2^20.  Both sides run the same betas on the same layer and must produce the same roots; they alternate within
 one process, after a warm-up of both, and each sample is a host clock around a call that ends blocked on the device.  The condition,
 written down before the first run: the single call is not slower (median) than the composed sequence at any of the three sizes.
-It is reported as measured; exit status 2 when it does not hold."""
+It is reported as measured; exit status 2 when it does not hold.
+
+--transcript (with or without --ext): the commit phase on the device transcript (include/toyni_hip.h 3l) against the callback phase,
+m0 = 2^12, 2^16 and 2^20 down to 16, salted.  (a) the callback phase, the yardstick: toyni_fri_commit_phase[_ext]_device with the
+transcript of tests/harness (hashlib behind a ctypes callback -- what the Python provers pay per round; a compiled caller's callback is
+cheaper by the interpreter's share); (new) toyni_fri_commit_phase_transcript[_ext]_device followed by one stream synchronisation, the
+1 KiB upload of the initial transcript included.  --tail-log N sets TOYNI_FRI_TAIL_LOG for the process before the first call (the knob
+is read once): -1 is variant (b), every round launched; the default is variant (c), the fused small rounds.  Both sides start from the
+same transcript and must leave the same layers, trees and transcript; they alternate within one process after a warm-up of both.
+With the fused tail a captured graph of the new phase at 2^16 is replayed as well (replay + synchronisation)."""
 import argparse
 import ctypes
 import os
@@ -187,10 +196,116 @@ def main_ext(reps, warmup):
     return 0
 
 
+# ---- --transcript ----
+def transcript_case(ctx, ext, log_m0, reps, warmup, with_graph):
+    import hashlib
+    from toyni_amd import prover as pv
+    dev = torch.device("cuda", 0)
+    words = 4 if ext else 1
+    m0 = 1 << log_m0
+    halves = [m0 >> (k + 1) for k in range(log_m0 - EXT_FINAL.bit_length() + 1)]
+    layer0 = torch.randint(0, P, (words * m0,), dtype=torch.int32, device=dev)
+    salts = torch.randint(0, 256, (sum(halves[:-1]), 16), dtype=torch.uint8, device=dev)
+    ndig = [lib.toyni_merkle_total_digests(h) for h in halves]
+    out = {name: (torch.empty(words * sum(halves), dtype=torch.int32, device=dev), torch.empty((sum(ndig), 32), dtype=torch.uint8, device=dev))
+           for name in ("callback", "device")}
+    state0 = hashlib.sha256(b"toyni-stark-v1").digest() + bytes(range(32))      # a transcript that has squeezed and absorbed one root
+    final = {}
+
+    def callback():
+        t = [state0]
+
+        def squeeze():
+            t[0] = hashlib.sha256(t[0]).digest()
+            return int.from_bytes(t[0][:8], "little") % P
+
+        def challenge(_rnd, root, want_beta):
+            if root is not None:
+                t[0] += root
+            if not want_beta:
+                return 0
+            return [squeeze() for _ in range(4)] if ext else squeeze()
+
+        layers, levels = out["callback"]
+        entry = pv.fri_commit_phase_ext_device if ext else pv.fri_commit_phase_device
+        entry(ctx, layer0.data_ptr(), m0, EXT_X0, EXT_FINAL, salts.data_ptr(), challenge, layers.data_ptr(), levels.data_ptr())
+        final["callback"] = t[0]
+
+    tr = pv.DeviceTranscript()
+    entry_dev = pv.fri_commit_phase_transcript_ext_device if ext else pv.fri_commit_phase_transcript_device
+    s = torch.cuda.Stream(device=dev)
+
+    def enqueue(stream):
+        layers, levels = out["device"]
+        entry_dev(ctx, layer0.data_ptr(), m0, EXT_X0, EXT_FINAL, salts.data_ptr(), tr, layers.data_ptr(), levels.data_ptr(), 0, stream)
+
+    def device():
+        tr.load(state0, s.cuda_stream)
+        enqueue(s.cuda_stream)
+        ctx.synchronize(s.cuda_stream)
+
+    samples = {"callback": [], "device": []}
+    for r in range(warmup + reps):
+        for name, f in (("callback", callback), ("device", device)) if r % 2 == 0 else (("device", device), ("callback", callback)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            f()
+            t1 = time.perf_counter()
+            if r >= warmup:
+                samples[name].append((t1 - t0) * 1e6)
+    torch.cuda.synchronize()
+    assert torch.equal(out["callback"][0], out["device"][0]) and torch.equal(out["callback"][1], out["device"][1]), "the two phases disagree"
+    assert tr.download() == (final["callback"], 0), "the two transcripts disagree"
+    if with_graph:
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            enqueue(s.cuda_stream)
+        samples["graph"] = []
+        for r in range(warmup + reps):
+            tr.load(state0, s.cuda_stream)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            g.replay()
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            if r >= warmup:
+                samples["graph"].append((t1 - t0) * 1e6)
+        assert torch.equal(out["callback"][0], out["device"][0]) and tr.download() == (final["callback"], 0), "the replay disagrees"
+        del g
+    tr.free()
+    return len(halves), samples
+
+
+def main_transcript(ext, reps, warmup, tail_log):
+    if tail_log is not None:
+        os.environ["TOYNI_FRI_TAIL_LOG"] = str(tail_log)
+    knob = os.environ.get("TOYNI_FRI_TAIL_LOG", "default")
+    fused = knob != "-1"
+    ctx = toyni_amd.NttContext(1 << max(EXT_SIZES))
+    print(f"{'Ext' if ext else 'base'} FRI commit phase on the device transcript, TOYNI_FRI_TAIL_LOG={knob} "
+          f"({'variant (c): fused small rounds' if fused else 'variant (b): every round launched'}), final_size {EXT_FINAL}, salted, x0 {EXT_X0}; "
+          f"{reps} alternating samples after {warmup} warm-up rounds of both; host clock around calls that end in a synchronisation; "
+          f"device {torch.cuda.get_device_name(0)}")
+    for log_m0 in EXT_SIZES:
+        rounds, s = transcript_case(ctx, ext, log_m0, reps, warmup, with_graph=fused and log_m0 == 16)
+        a, b = statistics.median(s["callback"]), statistics.median(s["device"])
+        print(f"m0 = 2^{log_m0} ({rounds} rounds)")
+        print(f"  (a) callback phase, hashlib transcript      {spread(s['callback'])}")
+        print(f"  ({'c' if fused else 'b'}) device transcript + synchronise        {spread(s['device'])}")
+        print(f"  (a) / new = {a / b:.3f}   ({(a - b) / rounds:+.1f} us per round; the new call {'beats' if b < a else 'DOES NOT beat'} (a))")
+        if "graph" in s:
+            print(f"  (c) captured graph, replay + synchronise    {spread(s['graph'])}")
+    return 0
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--ext", action="store_true", help="the Ext commit phase against the composed sequence (see above)")
+    ap.add_argument("--transcript", action="store_true", help="the commit phase on the device transcript against the callback phase (see above)")
+    ap.add_argument("--tail-log", type=int, default=None, help="with --transcript: TOYNI_FRI_TAIL_LOG for this process (-1: every round launched)")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
     args = ap.parse_args()
+    if args.transcript:
+        sys.exit(main_transcript(args.ext, args.reps, args.warmup, args.tail_log))
     sys.exit(main_ext(args.reps, args.warmup) if args.ext else main())

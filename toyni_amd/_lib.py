@@ -141,6 +141,15 @@ SIGNATURES = {
     "toyni_fri_fold_commit_ext_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_void_p, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_ext_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                   c_void_p, ctypes.POINTER(ctypes.c_uint), c_void_p]),
+    # section 3l
+    "toyni_transcript_absorb_device": (c_int, [c_void_p, c_void_p, c_size, c_void_p]),
+    "toyni_transcript_squeeze_device": (c_int, [c_void_p, c_void_p, c_size, c_void_p]),
+    "toyni_transcript_squeeze_indices_device": (c_int, [c_void_p, c_size, c_u32, c_void_p, c_void_p]),
+    "toyni_fri_query_positions_device": (c_int, [c_void_p, c_size, c_size, c_size, c_void_p, c_void_p]),
+    "toyni_fri_commit_phase_transcript_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                         c_void_p, c_void_p]),
+    "toyni_fri_commit_phase_transcript_ext_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                             c_void_p, c_void_p]),
     # section 3c
     "toyni_fri_fold_commit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -199,6 +199,11 @@ TOYNI_HD uint32_t mont_inv_chain(uint32_t aR) {
 }
 TOYNI_HD uint32_t to_mont(uint32_t a) { return mont_mul(a, BB_R2); }
 TOYNI_HD uint32_t from_mont(uint32_t aR) { return mont_mul(aR, 1u); }
+// Any u64 -> its canonical residue: BabyBear::new of from_bytes_mod_order (src/babybear.rs:65-71), the reference's `u64 % p`.
+// x = hi 2^32 + lo, and a Montgomery product takes ANY u32 on the left: mont_mul(hi, R^2) = hi R = hi 2^32 mod p and
+// mont_mul(lo, R) = lo mod p, both canonical, so the whole reduction is two products and one add and has no operand domain of its
+// own to state -- every u64 is valid; the three primitives it is built from report to the contract hook themselves.
+TOYNI_HD uint32_t bb_reduce_u64(uint64_t x) { return bb_add(mont_mul((uint32_t)(x >> 32), BB_R2), mont_mul((uint32_t)x, BB_R1)); }
 
 // ---- plain products (host-side table building, cross-checks) ----
 // The north-star's "64-bit Barrett": q = hi64(prod * MU), r = prod - q p, one conditional subtract

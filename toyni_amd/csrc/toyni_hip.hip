@@ -25,6 +25,7 @@
 #include "ntt_plan.hpp"
 #include "merkle_kernels.hpp"
 #include "prover_kernels.hpp"
+#include "transcript_kernels.hpp"
 
 using namespace toyni;
 
@@ -1617,6 +1618,236 @@ __global__ void __launch_bounds__(MERKLE_TAIL_T) merkle_tail_kernel(const Digest
     if (notify && threadIdx.x == 0) merkle_notify(lvl[0], notify, seq);
 }
 
+// ---- the Fiat-Shamir transcript in device memory (transcript_kernels.hpp; include/toyni_hip.h 3l) ----
+// Every kernel here is ONE wave: the chains are serial, one lane runs them; the lanes share only the byte copy of an absorb and, in
+// the index squeeze (where every lane computes the same hashes: uniform branches throughout), the search of the values seen so far.
+static_assert(sizeof(toyni_transcript) == sizeof(TranscriptState) && offsetof(toyni_transcript, bytes) == offsetof(TranscriptState, bytes) &&
+              offsetof(toyni_transcript, status) == offsetof(TranscriptState, status) && TOYNI_TRANSCRIPT_CAPACITY == TRANSCRIPT_CAPACITY &&
+              TOYNI_E_RANGE == TRANSCRIPT_E_RANGE, "toyni_transcript of the header");
+constexpr uint32_t TRANSCRIPT_T = 64;
+__global__ void __launch_bounds__(TRANSCRIPT_T) transcript_absorb_kernel(TranscriptState* __restrict__ tr, const uint8_t* __restrict__ src, uint32_t n) {
+    transcript_absorb_wave(*tr, src, n, threadIdx.x, TRANSCRIPT_T);
+}
+__global__ void __launch_bounds__(TRANSCRIPT_T) transcript_squeeze_kernel(TranscriptState* __restrict__ tr, uint32_t* __restrict__ out, uint32_t count) {
+    if (threadIdx.x == 0) transcript_squeeze(*tr, out, count);
+}
+__global__ void __launch_bounds__(TRANSCRIPT_T) transcript_squeeze_indices_kernel(TranscriptState* __restrict__ tr, uint32_t count, uint32_t max,
+                                                                                   uint32_t* __restrict__ out) {
+    __shared__ uint32_t seen[TRANSCRIPT_MAX_INDICES];
+    __shared__ uint32_t flag;
+    // "some lane found it": through one LDS word.  The LDS operations of a wave execute in program order, so clear / set / read need
+    // no barrier, only the compiler kept from moving them.
+    const auto any_lane = [](bool hit) {
+        if (threadIdx.x == 0) flag = 0u;
+        TOYNI_WAVE_ORDER();
+        if (hit) flag = 1u;
+        TOYNI_WAVE_ORDER();
+        const uint32_t some = flag;
+        TOYNI_WAVE_ORDER();
+        return some != 0u;
+    };
+    transcript_squeeze_indices(*tr, count, max, out, seen, threadIdx.x, TRANSCRIPT_T, any_lane);
+}
+__global__ void __launch_bounds__(256) fri_query_positions_kernel(const uint32_t* __restrict__ indices, uint32_t count, uint64_t m0, uint64_t total,
+                                                                  uint32_t* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) out[t] = fri_query_position(indices, count, m0, t);
+}
+
+// ---- the commit phase on that transcript (include/toyni_hip.h 3l) ----
+// Between two rounds, one wave: absorb the root the tree's last kernel has just written (root != nullptr), then squeeze the next
+// round's beta (nsqueeze = 1, or 4 for an Ext beta; 0 after the last round) and leave it in device memory in the form the next fold
+// consumes -- the host cannot: it never sees beta.  rec[k] = beta_k c0 in Montgomery form, rec[4 + k] = beta_k c1 likewise (Ext
+// only), c0 / c1 = host constants times R^2: base c0 = 1 / (2 x_k); Ext c0 = 1 / 2, c1 = 11 / 2, which makes rec an ExtFactor of
+// beta / 2.  betas (optional) receives the plain canonical coordinates.  A transcript whose status is set gives beta = 0.
+__global__ void __launch_bounds__(TRANSCRIPT_T) fri_transcript_round_kernel(TranscriptState* __restrict__ tr, const uint8_t* __restrict__ root,
+                                                                             uint32_t nsqueeze, uint32_t c0, uint32_t c1, uint32_t* __restrict__ rec,
+                                                                             uint32_t* __restrict__ betas) {
+    __shared__ uint32_t beta[4];
+    if (threadIdx.x == 0) {
+        if (root) transcript_absorb(*tr, root, 32u);
+        transcript_squeeze(*tr, beta, nsqueeze);
+    }
+    if (nsqueeze == 0u) return;
+    __syncthreads();
+    if (threadIdx.x < nsqueeze) {
+        const uint32_t b = beta[threadIdx.x];
+        if (betas) betas[threadIdx.x] = b;
+        rec[threadIdx.x] = transcript_factor(b, c0);
+        if (nsqueeze == 4u) rec[4u + threadIdx.x] = transcript_factor(b, c1);
+    }
+}
+
+// The folds of that phase: fri_fold_kernel<.., COMMIT> and fri_fold_ext_commit_kernel with the challenge's factor read from the
+// record the kernel above left, instead of from the launch arguments.  One output and one leaf hash per thread, grid-stride.
+__global__ void __launch_bounds__(256) fri_fold_commit_rec_kernel(const FoldArgs f0, const uint32_t* __restrict__ rec, const uint4* __restrict__ salts,
+                                                                  Digest* __restrict__ leaves) {
+    FoldArgs f = f0;
+    f.coef = rec[0];
+    const uint64_t half = f.half;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < half; i += stride) {
+        const uint32_t r = fold_one(f, i, f.evals[i], f.evals[i + half]);
+        f.out[i] = r;
+        if (salts) {
+            const uint4 sv = salts[i];
+            const uint32_t sw[4] = {sv.x, sv.y, sv.z, sv.w};
+            leaves[i] = merkle_leaf(r, sw);
+        } else {
+            leaves[i] = merkle_leaf(r, nullptr);
+        }
+    }
+}
+template <bool SALTED>
+__global__ void __launch_bounds__(256) fri_fold_ext_commit_rec_kernel(const FoldArgs f, const ExtFactor* __restrict__ rec, const uint4* __restrict__ salts,
+                                                                      Digest* __restrict__ leaves) {
+    const ExtFactor beta_half = *rec;
+    const uint64_t half = f.half;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint4* ea = reinterpret_cast<const uint4*>(f.evals);
+    const uint4* eb = ea + half;
+    uint4* o = reinterpret_cast<uint4*>(f.out);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < half; i += stride) {
+        const uint32_t scaleR = mont_mul(subdomain_mont(f.dom, (uint32_t)i), f.coef);
+        const uint4 a = ea[i], b = eb[i];
+        uint32_t sw[4] = {0u, 0u, 0u, 0u};
+        if constexpr (SALTED) {
+            const uint4 s = salts[i];
+            sw[0] = s.x; sw[1] = s.y; sw[2] = s.z; sw[3] = s.w;
+        }
+        const FoldExtLeaf r = fold_ext_commit_one<SALTED>(Ext4{{a.x, a.y, a.z, a.w}}, Ext4{{b.x, b.y, b.z, b.w}}, scaleR, beta_half, sw);
+        o[i] = make_uint4(r.folded.c[0], r.folded.c[1], r.folded.c[2], r.folded.c[3]);
+        leaves[i] = r.leaf;
+    }
+}
+
+// ALL remaining rounds of a transcript commit phase in ONE workgroup, from the first round whose folded layer has at most MERKLE_TAIL
+// leaves: a round that small is a chain of dependent compressions in which every launch boundary costs about what the hash it
+// separates does, and with beta produced on the device nothing between two rounds needs the host.  The layer (folded in place: thread
+// i reads elements i and i + half and writes element i, which no other thread touches in that round), the tree level, the two-wave
+// schedule areas and the transcript itself live in LDS; every layer and every level is also written to global memory.  Per round:
+//   thread 0: absorb the previous root (from the level array), squeeze beta                                | barrier
+//   thread i < half: fold, leaf hash from the registers that hold the folded element (the last layer unsalted)  | barrier
+//   the node levels with merkle_node_coop, as merkle_tail_kernel runs them (its barriers)
+// and after the last round thread 0 absorbs the last root and the transcript goes back to global memory.  Round r of the launch folds on
+// the points of a.dom at stride 2^r (w_{m/2} = w_m^2) and on x^(2^r): one SubDomain and one x^-1 serve every round.  Every loop count
+// and every barrier condition is decided from m: wave-uniform.
+struct FriTailArgs {
+    const uint32_t* cur;     // the layer the first fused round folds: m elements
+    uint32_t* out;           // the folded layers, back to back
+    Digest* levels;          // their trees, back to back
+    const uint4* salts;      // 16 bytes per leaf of every salted layer back to back (the final layer has none), or nullptr
+    TranscriptState* tr;
+    uint32_t* betas;         // the plain canonical beta of every round, or nullptr
+    SubDomain dom;           // winv_N^(i << s) for the first fused round's m (Montgomery)
+    uint32_t m, final_size;
+    uint32_t xinvR;          // Montgomery form of 1 / x of the first fused round
+    uint32_t half_r2, half11_r2;   // (1 / 2) R^2 and (11 / 2) R^2: transcript_factor
+};
+template <bool EXT>
+__global__ void __launch_bounds__(MERKLE_TAIL_T) fri_tail_rounds_kernel(const FriTailArgs a) {
+    constexpr uint32_t W = EXT ? 4u : 1u, NSQ = EXT ? 4u : 1u;
+    __shared__ uint32_t layer[2 * MERKLE_TAIL * W];
+    __shared__ Digest lvl[MERKLE_TAIL];
+    __shared__ uint32_t sched[MERKLE_TAIL_T / 128][COOP_SCHED_WORDS];
+    __shared__ TranscriptState tr;
+    __shared__ uint32_t beta[4];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = TOYNI_UNIFORM(tid >> 6);
+    const uint32_t pair = wave >> 1;
+    const bool helper = (wave & 1u) != 0u;
+    for (uint32_t i = tid; i < a.m * W; i += blockDim.x) layer[i] = a.cur[i];
+    for (uint32_t i = tid; i < TRANSCRIPT_CAPACITY; i += blockDim.x) tr.bytes[i] = a.tr->bytes[i];
+    if (tid == 0) { tr.len = a.tr->len; tr.status = a.tr->status; }
+    __syncthreads();
+    uint32_t m = a.m, shift = 0, xinvR = a.xinvR;
+    uint32_t* out = a.out;
+    Digest* levels = a.levels;
+    const uint4* salts = a.salts;
+    uint32_t* betas = a.betas;
+    bool have_root = false;
+    while (m > a.final_size) {
+        const uint32_t half = m >> 1;
+        const bool salted = salts && half != a.final_size;
+        if (tid == 0u) {
+            if (have_root) transcript_absorb(tr, reinterpret_cast<const uint8_t*>(&lvl[0]), 32u);
+            transcript_squeeze(tr, beta, NSQ);
+            if (betas) {
+#pragma unroll
+                for (uint32_t k = 0; k < NSQ; ++k) betas[k] = beta[k];
+            }
+        }
+        __syncthreads();   // beta is there; the root has been read before a leaf of this round replaces it
+        if (tid < half) {
+            uint32_t sw[4] = {0u, 0u, 0u, 0u};
+            if (salted) {
+                const uint4 sv = salts[tid];
+                sw[0] = sv.x; sw[1] = sv.y; sw[2] = sv.z; sw[3] = sv.w;
+            }
+            Digest d;
+            if constexpr (EXT) {
+                ExtFactor f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { f.b[k] = transcript_factor(beta[k], a.half_r2); f.b11[k] = transcript_factor(beta[k], a.half11_r2); }
+                const uint32_t scaleR = mont_mul(subdomain_mont(a.dom, tid << shift), xinvR);
+                const uint32_t* pa = layer + 4u * tid;
+                const uint32_t* pb = layer + 4u * (tid + half);
+                const Ext4 va{{pa[0], pa[1], pa[2], pa[3]}}, vb{{pb[0], pb[1], pb[2], pb[3]}};
+                const FoldExtLeaf r = salted ? fold_ext_commit_one<true>(va, vb, scaleR, f, sw) : fold_ext_commit_one<false>(va, vb, scaleR, f, sw);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) layer[4u * tid + (uint32_t)k] = r.folded.c[k];
+                reinterpret_cast<uint4*>(out)[tid] = make_uint4(r.folded.c[0], r.folded.c[1], r.folded.c[2], r.folded.c[3]);
+                d = r.leaf;
+            } else {
+                FoldArgs f{};
+                f.dom = a.dom;
+                f.coef = mont_mul(transcript_factor(beta[0], a.half_r2), xinvR);   // Montgomery form of beta / (2 x)
+                const uint32_t r = fold_one(f, (uint64_t)(tid << shift), layer[tid], layer[tid + half]);
+                layer[tid] = r;
+                out[tid] = r;
+                if (salted) d = merkle_leaf(r, sw);
+                else d = merkle_leaf(r, nullptr);
+            }
+            lvl[tid] = d;
+            levels[tid] = d;
+        }
+        __syncthreads();   // the leaves, and the folded layer, before anything reads them
+        uint32_t n = half;
+        Digest* next = levels + half;
+        while (n > 1u) {
+            const uint32_t up = (n + 1u) / 2u;
+            const bool active = pair * 64u < up;               // wave-uniform
+            const uint32_t i0 = pair * 64u + lane;
+            const uint32_t i = i0 < up ? i0 : up - 1u;
+            Digest l{}, r{};
+            if (active) {
+                l = lvl[2u * i];
+                r = (2u * i + 1u < n) ? lvl[2u * i + 1u] : l;
+            }
+            const Digest d = merkle_node_coop(l, r, sched[pair], lane, helper, active);   // its first barrier: every read of the old level is done
+            if (active && !helper && i0 < up) {
+                lvl[i0] = d;
+                next[i0] = d;
+            }
+            TOYNI_LDS_BARRIER();
+            next += up;
+            n = up;
+        }
+        levels += 2u * half - 1u;
+        out += half * W;
+        if (salted) salts += half;
+        if (betas) betas += NSQ;
+        xinvR = mont_mul(xinvR, xinvR);   // the squared domain of the next layer
+        ++shift;
+        m = half;
+        have_root = true;
+    }
+    if (tid == 0u && have_root) transcript_absorb(tr, reinterpret_cast<const uint8_t*>(&lvl[0]), 32u);
+    __syncthreads();
+    for (uint32_t i = tid; i < TRANSCRIPT_CAPACITY; i += blockDim.x) a.tr->bytes[i] = tr.bytes[i];
+    if (tid == 0) { a.tr->len = tr.len; a.tr->status = tr.status; }
+}
+
 #ifndef TOYNI_KERNEL_TEXT_ONLY
 // ------------------------------------------------------------------------------------------------
 // context
@@ -1651,6 +1882,8 @@ struct toyni_ntt_ctx {
         size_t stage64_elems = 0;
         uint32_t* d_lde32 = nullptr;     // compact coefficient vectors of the LDE entry points
         size_t lde32_words = 0;
+        uint32_t* d_fri_rec = nullptr;   // the per-round beta records of the transcript commit phases (3l): FRI_REC_WORDS words, fixed
+        size_t fri_rec_words = 0;
         uint8_t* h_ring = nullptr;       // pinned staging ring: host tables that a stream-ordered copy reads after the call returned
         size_t ring_bytes = 0, ring_head = 0;
         uint64_t tick = 0;               // last use (eviction order)
@@ -1752,7 +1985,7 @@ void retire_scratch(toyni_ntt_ctx* c, toyni_ntt_ctx::Scratch& sc, hipStream_t s,
     // stream was last used, is what lets its buffers go (one event shared by the set's buffers: the last one to go destroys it)
     hipEvent_t ev = (sc.fenced && !sc.dirty) ? sc.fence : nullptr;
     bool handed = false;
-    for (void* p : {(void*)sc.d_work, (void*)sc.d_data32, (void*)sc.d_stage64, (void*)sc.d_lde32})
+    for (void* p : {(void*)sc.d_work, (void*)sc.d_data32, (void*)sc.d_stage64, (void*)sc.d_lde32, (void*)sc.d_fri_rec})
         if (p) { c->retired.push_back({p, s, stream_known, ev, false}); handed = true; }
     if (sc.fence && !(ev && handed)) (void)hipEventDestroy(sc.fence);
     if (sc.h_ring) (void)hipHostFree(sc.h_ring);   // waits for the copies that still read it (eviction, trim, destroy: never the steady state)
@@ -3367,6 +3600,156 @@ int toyni_fri_commit_phase_ext_device(toyni_ntt_ctx* c, const uint32_t* d_layer0
             if (!ext_beta_half(beta.v, &beta_half)) return (int)TOYNI_E_RANGE;
             return enqueue_fold_commit_ext(c, cur, out, m, beta_half, x, s, salts, levels, notify, seq);
         });
+}
+
+// ---- the transcript in device memory and the commit phases on it (include/toyni_hip.h 3l) ----
+static TranscriptState* transcript_of(toyni_transcript* d_tr) { return reinterpret_cast<TranscriptState*>(d_tr); }
+
+int toyni_transcript_absorb_device(toyni_transcript* d_tr, const uint8_t* d_bytes, size_t len, void* stream) {
+    if (!d_tr || (!d_bytes && len)) return TOYNI_E_NULL;
+    if (((uintptr_t)d_tr & 15) || len > TOYNI_TRANSCRIPT_CAPACITY) return TOYNI_E_RANGE;
+    if (len == 0) return TOYNI_OK;
+    hipLaunchKernelGGL(transcript_absorb_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, (hipStream_t)stream, transcript_of(d_tr), d_bytes, (uint32_t)len);
+    return (int)hipGetLastError();
+}
+
+int toyni_transcript_squeeze_device(toyni_transcript* d_tr, uint32_t* d_out, size_t count, void* stream) {
+    if (!d_tr || !d_out) return TOYNI_E_NULL;
+    if (((uintptr_t)d_tr & 15) || ((uintptr_t)d_out & 3) || count > 65536) return TOYNI_E_RANGE;
+    if (count == 0) return TOYNI_OK;
+    hipLaunchKernelGGL(transcript_squeeze_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, (hipStream_t)stream, transcript_of(d_tr), d_out, (uint32_t)count);
+    return (int)hipGetLastError();
+}
+
+int toyni_transcript_squeeze_indices_device(toyni_transcript* d_tr, size_t count, uint32_t max, uint32_t* d_out, void* stream) {
+    if (!d_tr || !d_out) return TOYNI_E_NULL;
+    if (((uintptr_t)d_tr & 15) || ((uintptr_t)d_out & 3)) return TOYNI_E_RANGE;
+    if (count == 0 || count > TRANSCRIPT_MAX_INDICES || max == 0 || count > max) return TOYNI_E_RANGE;
+    hipLaunchKernelGGL(transcript_squeeze_indices_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, (hipStream_t)stream, transcript_of(d_tr), (uint32_t)count, max,
+                       d_out);
+    return (int)hipGetLastError();
+}
+
+int toyni_fri_query_positions_device(const uint32_t* d_indices, size_t count, size_t m0, size_t final_size, uint32_t* d_out, void* stream) {
+    if (!d_indices || !d_out) return TOYNI_E_NULL;
+    if (((uintptr_t)d_indices & 3) || ((uintptr_t)d_out & 3)) return TOYNI_E_RANGE;
+    if (!is_pow2(m0) || !is_pow2(final_size) || final_size < 1 || (uint64_t)m0 > ((uint64_t)1 << 32) || count > 65536) return TOYNI_E_RANGE;
+    if (count == 0 || m0 <= final_size) return TOYNI_OK;
+    const uint64_t total = (uint64_t)(ilog2(m0) - ilog2(final_size)) * 2u * count;
+    hipLaunchKernelGGL(fri_query_positions_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, d_indices, (uint32_t)count, (uint64_t)m0,
+                       total, d_out);
+    return (int)hipGetLastError();
+}
+
+// The loop of both transcript phases (arguments checked by the entry points; m0 > final_size).  `words` = u32 words per layer
+// element.  Round k: its fold reads record k of the stream's buffer -- written by the one-wave kernel that closed round k - 1 (or
+// opened the phase) -- then the node levels, then that kernel again: absorb the root, squeeze, record k + 1.  One linear chain.
+constexpr size_t FRI_REC_STRIDE = sizeof(ExtFactor) / sizeof(uint32_t);   // words per record (the base phase uses the first)
+constexpr size_t FRI_REC_WORDS = 32 * FRI_REC_STRIDE;                     // a layer has at most 2^27 elements: fewer than 32 rounds
+static int commit_phase_transcript(toyni_ntt_ctx* c, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size, size_t words,
+                                   const uint8_t* d_salts, toyni_transcript* d_tr, uint32_t* d_layers, uint8_t* d_levels, uint32_t* d_betas,
+                                   hipStream_t s) {
+    const bool ext = words == 4;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    if (int rc = grow(c, s, (void**)&sc.d_fri_rec, &sc.fri_rec_words, FRI_REC_WORDS, sizeof(uint32_t))) return rc;
+    TranscriptState* tr = transcript_of(d_tr);
+    const uint32_t nsq = ext ? 4u : 1u;
+    // the host constants of a record, times R^2 (transcript_factor): Ext 1 / 2 and 11 / 2; base 1 / (2 x_k), per round
+    const uint32_t half_r2 = to_mont_host(to_mont_host(BB_HALF)), half11_r2 = to_mont_host(to_mont_host(bb_mul_host(BB_HALF, 11u)));
+    const auto base_r2 = [](uint32_t x) { return to_mont_host(to_mont_host(bb_mul_host(BB_HALF, bb_inv_host(x)))); };
+    const uint32_t* cur = d_layer0;
+    uint32_t* out = d_layers;
+    uint8_t* levels = d_levels;
+    const uint8_t* salts = d_salts;
+    uint32_t* betas = d_betas;
+    uint32_t x = x0;
+    uint32_t* rec = sc.d_fri_rec;
+    // From the first round whose folded layer has at most 2^TOYNI_FRI_TAIL_LOG leaves (default 9 = MERKLE_TAIL, the largest possible;
+    // -1 = never: A/B runs), one workgroup runs all remaining rounds (fri_tail_rounds_kernel); it squeezes its own first beta.
+    static const int tail_log = std::min(env_int("TOYNI_FRI_TAIL_LOG", 9), ilog2(MERKLE_TAIL));
+    const size_t tail_leaves = tail_log < 0 ? 0 : (size_t)1 << tail_log;
+    size_t m = m0;
+    if ((m >> 1) > tail_leaves)
+        hipLaunchKernelGGL(fri_transcript_round_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, s, tr, static_cast<const uint8_t*>(nullptr), nsq,
+                           ext ? half_r2 : base_r2(x), half11_r2, rec, betas);
+    for (; m > final_size && (m >> 1) > tail_leaves; m >>= 1) {
+        const size_t half = m >> 1;
+        const bool last = half == final_size;
+        const size_t digests = toyni_merkle_total_digests(half);
+        const uint4* round_salts = reinterpret_cast<const uint4*>(last ? nullptr : salts);
+        Digest* leaves = reinterpret_cast<Digest*>(levels);
+        FoldArgs f{};
+        f.evals = cur;
+        f.out = out;
+        f.dom = sub_domain(c->plan, c->d_inv, c->plan.log_n - ilog2(m));
+        f.half = half;
+        const dim3 grid(grid_for(half)), block(256);
+        if (ext) {
+            f.coef = to_mont_host(bb_inv_host(x));
+            const ExtFactor* r = reinterpret_cast<const ExtFactor*>(rec);
+            if (round_salts) hipLaunchKernelGGL((fri_fold_ext_commit_rec_kernel<true>), grid, block, 0, s, f, r, round_salts, leaves);
+            else hipLaunchKernelGGL((fri_fold_ext_commit_rec_kernel<false>), grid, block, 0, s, f, r, round_salts, leaves);
+        } else {
+            hipLaunchKernelGGL(fri_fold_commit_rec_kernel, grid, block, 0, s, f, (const uint32_t*)rec, round_salts, leaves);
+        }
+        if (int rc = enqueue_merkle_upper(levels, half, s)) return rc;
+        const uint8_t* root = levels + (digests - 1) * 32;
+        cur = out;
+        out += half * words;
+        levels += digests * 32;
+        if (salts && !last) salts += half * 16;
+        if (betas) betas += nsq;
+        x = bb_mul_host(x, x);   // the squared domain of the next layer, src/fibonacci.rs:228-231
+        rec += FRI_REC_STRIDE;
+        const bool tail_next = (half >> 1) <= tail_leaves;   // the fused rounds squeeze for themselves
+        hipLaunchKernelGGL(fri_transcript_round_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, s, tr, root, last || tail_next ? 0u : nsq,
+                           ext ? half_r2 : base_r2(x), half11_r2, rec, betas);
+    }
+    if (m > final_size) {
+        FriTailArgs a{};
+        a.cur = cur;
+        a.out = out;
+        a.levels = reinterpret_cast<Digest*>(levels);
+        a.salts = reinterpret_cast<const uint4*>(salts);
+        a.tr = tr;
+        a.betas = betas;
+        a.dom = sub_domain(c->plan, c->d_inv, c->plan.log_n - ilog2(m));
+        a.m = (uint32_t)m;
+        a.final_size = (uint32_t)final_size;
+        a.xinvR = to_mont_host(bb_inv_host(x));
+        a.half_r2 = half_r2;
+        a.half11_r2 = half11_r2;
+        if (ext) hipLaunchKernelGGL((fri_tail_rounds_kernel<true>), dim3(1), dim3(MERKLE_TAIL_T), 0, s, a);
+        else hipLaunchKernelGGL((fri_tail_rounds_kernel<false>), dim3(1), dim3(MERKLE_TAIL_T), 0, s, a);
+    }
+    return (int)hipGetLastError();
+}
+
+int toyni_fri_commit_phase_transcript_device(toyni_ntt_ctx* c, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size,
+                                             const uint8_t* d_salts, toyni_transcript* d_tr, uint32_t* d_layers, uint8_t* d_levels,
+                                             uint32_t* d_betas, void* stream) {
+    if (!c || !d_layer0 || !d_tr || !d_layers || !d_levels) return TOYNI_E_NULL;
+    if (!is_pow2(m0) || !is_pow2(final_size) || final_size < 1 || m0 > c->n) return TOYNI_E_INVALID_SIZE;
+    if (x0 == 0 || x0 >= BB_P) return TOYNI_E_RANGE;
+    if (((uintptr_t)d_levels & 15) || ((uintptr_t)d_salts & 15) || ((uintptr_t)d_tr & 15) || ((uintptr_t)d_betas & 3)) return TOYNI_E_RANGE;
+    if (m0 <= final_size) return TOYNI_OK;
+    return commit_phase_transcript(c, d_layer0, m0, x0, final_size, 1, d_salts, d_tr, d_layers, d_levels, d_betas, (hipStream_t)stream);
+}
+
+int toyni_fri_commit_phase_transcript_ext_device(toyni_ntt_ctx* c, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size,
+                                                 const uint8_t* d_salts, toyni_transcript* d_tr, uint32_t* d_layers, uint8_t* d_levels,
+                                                 uint32_t* d_betas, void* stream) {
+    if (!c || !d_layer0 || !d_tr || !d_layers || !d_levels) return TOYNI_E_NULL;
+    if (!is_pow2(m0) || !is_pow2(final_size) || final_size < 1) return TOYNI_E_INVALID_SIZE;
+    if (x0 == 0) return TOYNI_E_ZERO_INVERSE;
+    if (x0 >= BB_P) return TOYNI_E_RANGE;
+    if ((((uintptr_t)d_layer0 | (uintptr_t)d_layers | (uintptr_t)d_levels | (uintptr_t)d_salts | (uintptr_t)d_tr) & 15) || ((uintptr_t)d_betas & 3))
+        return TOYNI_E_RANGE;
+    if (m0 > c->n) return TOYNI_E_INVALID_SIZE;
+    if (m0 <= final_size) return TOYNI_OK;
+    return commit_phase_transcript(c, d_layer0, m0, x0, final_size, 4, d_salts, d_tr, d_layers, d_levels, d_betas, (hipStream_t)stream);
 }
 
 static DomainArgs domain_args(toyni_ntt_ctx* c, unsigned log_m, uint32_t shift) {

@@ -492,6 +492,92 @@ def column_scan_ext_device(ctx, num, den, out: int, out_stride: int, n: int, bat
                                            out, out_stride, n, batch, op, i.ctypes.data, totals or None, stream or None), "GPU Ext column scan failed")
 
 
+# ---- the Fiat-Shamir transcript in device memory and the commit phases on it (include/toyni_hip.h 3l) ----
+TRANSCRIPT_CAPACITY = 1008
+
+
+class DeviceTranscript:
+    """toyni_transcript: FiatShamirTranscript (src/transcript.rs) as 1024 bytes of device memory.  Every method but `download` and
+    `status` only enqueues on `stream`; outputs are device pointers.  What the host cannot check -- an absorb beyond the capacity --
+    sets the sticky status word, after which every operation writes zeros: read `status()` once the work has been synchronised."""
+
+    def __init__(self):
+        p = ctypes.c_void_p()
+        check(lib.toyni_malloc(ctypes.byref(p), 1024), "device allocation of a transcript failed")
+        self.ptr = p.value
+        self._staged = []    # host copies that an enqueued upload may still read
+
+    @classmethod
+    def from_bytes(cls, state: bytes = b"toyni-stark-v1", stream: int = 0) -> "DeviceTranscript":
+        tr = cls()
+        tr.load(state, stream)
+        return tr
+
+    def load(self, state: bytes, stream: int = 0) -> None:
+        """Replace the transcript by `state` (status cleared): one stream-ordered upload of a host copy, no kernel."""
+        if len(state) > TRANSCRIPT_CAPACITY:
+            raise ValueError(f"a device transcript holds at most {TRANSCRIPT_CAPACITY} bytes")
+        host = np.zeros(1024, dtype=np.uint8)
+        host[:4] = np.frombuffer(np.uint32(len(state)).tobytes(), dtype=np.uint8)
+        host[16:16 + len(state)] = np.frombuffer(bytes(state), dtype=np.uint8)
+        self._staged = self._staged[-7:] + [host]
+        check(lib.toyni_memcpy_h2d_async(self.ptr, host.ctypes.data, 1024, stream or None), "upload of a transcript failed")
+
+    def absorb_device(self, d_bytes: int, length: int, stream: int = 0) -> None:
+        check(lib.toyni_transcript_absorb_device(self.ptr, d_bytes or None, length, stream or None), "GPU transcript absorb failed")
+
+    def squeeze(self, d_out: int, count: int = 1, stream: int = 0) -> None:
+        """`count` challenges (canonical residues) to d_out; an Ext challenge is count = 4."""
+        check(lib.toyni_transcript_squeeze_device(self.ptr, d_out, count, stream or None), "GPU transcript squeeze failed")
+
+    def squeeze_indices(self, d_out: int, count: int, mx: int, stream: int = 0) -> None:
+        """`count` distinct values below `mx`, in order of first appearance, to d_out."""
+        check(lib.toyni_transcript_squeeze_indices_device(self.ptr, count, mx, d_out, stream or None), "GPU transcript index squeeze failed")
+
+    def download(self):
+        """(state bytes, status) after a synchronous copy (the default stream: synchronise the stream that carries the work first)."""
+        host = np.zeros(1024, dtype=np.uint8)
+        check(lib.toyni_memcpy_d2h(host.ctypes.data, self.ptr, 1024), "download of a transcript failed")
+        length, status = (int(v) for v in host[:8].view(np.uint32))
+        return host[16:16 + min(length, TRANSCRIPT_CAPACITY)].tobytes(), status
+
+    def status(self) -> int:
+        return self.download()[1]
+
+    def free(self) -> None:
+        if self.ptr:
+            lib.toyni_free(self.ptr)
+            self.ptr = 0
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:  # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+def fri_query_positions_device(d_indices: int, count: int, m0: int, final_size: int, d_out: int, stream: int = 0) -> None:
+    """The positions `count` queries open in every layer but the final one: per layer k (m0 >> k elements) the pairs
+    [i mod half, i mod half + half], the layers back to back -- rounds x 2 count words."""
+    check(lib.toyni_fri_query_positions_device(d_indices, count, m0, final_size, d_out, stream or None), "GPU query positions failed")
+
+
+def fri_commit_phase_transcript_device(ctx, d_layer0: int, m0: int, x0: int, final_size: int, d_salts: int, transcript: DeviceTranscript,
+                                       d_layers: int, d_levels: int, d_betas: int = 0, stream: int = 0) -> None:
+    """fri_commit_phase_device with the transcript on the device: asynchronous, no callback; every beta is squeezed from
+    `transcript` and every root absorbed into it by kernels.  d_betas (optional): one word per round."""
+    check(lib.toyni_fri_commit_phase_transcript_device(ctx.handle, d_layer0, m0, x0, final_size, d_salts or None, transcript.ptr, d_layers,
+                                                       d_levels, d_betas or None, stream or None), "GPU FRI commit phase (device transcript) failed")
+
+
+def fri_commit_phase_transcript_ext_device(ctx, d_layer0: int, m0: int, x0: int, final_size: int, d_salts: int, transcript: DeviceTranscript,
+                                           d_layers: int, d_levels: int, d_betas: int = 0, stream: int = 0) -> None:
+    """The same over Ext-valued layers (four words per element, an Ext beta per round: d_betas takes four words per round)."""
+    check(lib.toyni_fri_commit_phase_transcript_ext_device(ctx.handle, d_layer0, m0, x0, final_size, d_salts or None, transcript.ptr, d_layers,
+                                                           d_levels, d_betas or None, stream or None),
+          "GPU Ext FRI commit phase (device transcript) failed")
+
+
 def merkle_open_record_bytes(n: int) -> int:
     return lib.toyni_merkle_open_record_bytes(n)
 
