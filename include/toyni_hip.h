@@ -637,6 +637,7 @@ int toyni_air_quotient_ext_device(toyni_ntt_ctx* ctx, const toyni_air_program* p
  *     beta exists.  The commit phases of 3c / 3j block on every round (a polled word, a host callback, a launch into an empty
  *     queue); the phases here are asynchronous, take no callback and can be captured into a HIP graph (caveat of section 4), and the
  *     path from the DEEP codeword to the opening records becomes stream-ordered: enqueue everything, synchronise once.
+ *     (3m runs the Ext phase on this transcript with FOUR-to-one rounds under coset leaves: half the rounds, lower trees.)
  *     The state has a public layout.  A caller initialises it with toyni_memcpy_h2d_async of a host copy (len = the bytes absorbed so
  *     far, status = 0, reserved = 0; the reference's transcript starts as the 14 bytes "toyni-stark-v1"); there is no init call.
  *     d_tr is device memory, 16-byte aligned.
@@ -689,6 +690,74 @@ int toyni_fri_commit_phase_transcript_device(toyni_ntt_ctx* ctx, const uint32_t*
 int toyni_fri_commit_phase_transcript_ext_device(toyni_ntt_ctx* ctx, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size,
                                                  const uint8_t* d_salts, toyni_transcript* d_tr, uint32_t* d_layers, uint8_t* d_levels,
                                                  uint32_t* d_betas, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * 3m. The Ext commit phase folding FOUR to one per round, under COSET leaves, on the device transcript of 3l.  The phases of 3c / 3j
+ *     / 3l are chains of dependent hashes -- a tree of log m - 1 levels per round, a serial squeeze between rounds -- and this
+ *     section makes that chain shorter instead of faster: half the rounds, each tree two levels lower.  The protocol shape is this
+ *     library's own (the reference, src/fibonacci.rs, folds two to one; its proof format is untouched).
+ *     A layer L of m Ext elements (AoS, section 3) lies on the points x_i = x0 w_m^i.  One round with the Ext challenge beta is
+ *         L'  = fri_fold_ext(L,  beta,   points x0   w_m^i)          (toyni_fri_fold_ext_device with x0)
+ *         L'' = fri_fold_ext(L', beta^2, points x0^2 w_(m/2)^i)      (toyni_fri_fold_ext_device with x0^2)
+ *     so L''[j] = f0 + beta f1 + beta^2 f2 + beta^3 f3 of the cubic through the coset {x, I x, -x, -I x}, I = w_m^(m/4), and depends
+ *     on exactly L[j], L[j + m/4], L[j + m/2], L[j + 3m/4].  The arithmetic is exact: the one-sweep kernel and the two calls agree
+ *     in every byte.
+ *     COSET LEAF: a committed layer of m >= 4 elements has m / 4 leaves,
+ *         leaf_j = [salt_j (16)] || to_bytes(L[j]) || to_bytes(L[j + m/4]) || to_bytes(L[j + m/2]) || to_bytes(L[j + 3m/4])
+ *     -- the row leaf of 3d with width 16, row j gathered from the four quarters of the layer.  00 || leaf is 145 bytes salted, 129
+ *     unsalted: three SHA-256 blocks either way.  Tree layout, node hash and opening record are 3d's with n = m / 4, width = 16:
+ *     toyni_merkle_total_digests(m / 4) digests, toyni_merkle_open_rows_record_bytes(m / 4, 16) bytes per record.
+ *     THE PHASE: layer k has m_k = m0 >> 2k elements on x0^(4^k) w_(m_k)^i; log2(m0 / final_size) is even and final_size >= 4; every
+ *     layer, the final one included, is committed under coset leaves, the final one unsalted.  The transcript sequence is 3l's with
+ *     half the rounds: the caller absorbs layer 0's root; per round four squeezes (an Ext beta), fold and commit, absorb the root.
+ *     Query indices are drawn with toyni_transcript_squeeze_indices_device(count, max = m0 / 4); query i opens leaf i mod (m_k / 4) of
+ *     layer k < R = log2(m0 / final_size) / 2, one record per layer; the final layer travels whole.
+ *     Alignment: every device pointer here is 16-byte aligned, except index and word arrays (d_indices, d_betas, the positions),
+ *     which are 4-byte aligned, and the opening records (d_out of the open call), 8-byte aligned as in 3d.
+ *     All calls are asynchronous on `stream`, enqueue linear chains of kernels and can be captured into a HIP graph (caveat of
+ *     section 4; the phase needs a warm context as in 3l).  There is no callback or blocking variant and no base-field variant.
+ * ---------------------------------------------------------------------------------------------- */
+/* The coset tree of a layer as it lies, and openings of it: byte for byte what toyni_merkle_commit_rows_device /
+ * toyni_merkle_open_rows_device (TOYNI_ROWS_ROW_MAJOR, width 16) write on a copy of the layer gathered into m / 4 rows of 16 words.
+ * d_salts = (m / 4) x 16 bytes or NULL; d_levels = toyni_merkle_total_digests(m / 4) x 32 bytes; d_indices: nidx leaf numbers, each
+ * below m / 4 (not checked, as in 3d); d_out: nidx records.  Layer 0 is committed, and every layer is opened, with these.
+ * m == 0 (and nidx == 0) succeeds and writes nothing.  Refused before anything is enqueued, the outputs untouched: TOYNI_E_NULL for
+ * a null d_layer, d_levels, d_indices or d_out; TOYNI_E_INVALID_SIZE for an m that is not a power of two or is below 4;
+ * TOYNI_E_RANGE for a misaligned pointer, m > 2^33 or nidx >= 2^32. */
+int toyni_merkle_commit_cosets_ext_device(const uint32_t* d_layer, size_t m, const uint8_t* d_salts, uint8_t* d_levels, void* stream);
+int toyni_merkle_open_cosets_ext_device(const uint8_t* d_levels, size_t m, const uint32_t* d_layer, const uint8_t* d_salts,
+                                        const uint32_t* d_indices, size_t nidx, uint8_t* d_out, void* stream);
+/* One four-to-one round in one sweep: d_out = L'' (m / 4 elements) and the coset tree of d_out in d_levels (m / 16 leaves; d_salts =
+ * (m / 16) x 16 bytes, or NULL for an unsalted tree).  One thread per leaf reads the 16 elements the leaf depends on, folds them in
+ * registers and hashes the leaf from the folded words; beta^2 is computed on the host.  d_out must not overlap d_evals; d_evals is
+ * only read.  m == 0 succeeds and writes nothing; m == 16 gives a tree of one digest, the leaf.
+ * Refused before anything is enqueued, the outputs untouched: TOYNI_E_NULL for a null ctx, d_evals, d_out, beta or d_levels;
+ * TOYNI_E_RANGE for an m that is not a power of two, is below 16 or exceeds the context's n; TOYNI_E_ZERO_INVERSE for x0 == 0;
+ * TOYNI_E_RANGE for x0 >= p, a beta coordinate >= p, or a device pointer that is not 16-byte aligned.  All of these but "m exceeds n"
+ * are decided on the arguments alone, before the context is read. */
+int toyni_fri_fold4_commit_ext_device(toyni_ntt_ctx* ctx, const uint32_t* d_evals, uint32_t* d_out, size_t m, const uint32_t beta[4],
+                                      uint32_t x0, const uint8_t* d_salts, uint8_t* d_levels, void* stream);
+/* The leaves the queries open: R lists of `count` words back to back, list k = d_indices[q] mod (m0 >> (2 k + 2)); each list feeds
+ * toyni_merkle_open_cosets_ext_device as it lies.  The refusals of toyni_fri_query_positions_device, and TOYNI_E_INVALID_SIZE for an
+ * odd log2(m0 / final_size) or final_size < 4; count == 0 or m0 <= final_size writes nothing. */
+int toyni_fri4_query_positions_device(const uint32_t* d_indices, size_t count, size_t m0, size_t final_size, uint32_t* d_out, void* stream);
+/* The phase.  Arguments as in toyni_fri_commit_phase_transcript_ext_device, with these sizes:
+ *   d_layers : out, the folded layers back to back: 4 (m0/4 + m0/16 + ... + final_size) words
+ *   d_salts  : 16 bytes per LEAF of every salted folded layer back to back (m0/16 + m0/64 + ... leaves, the final layer excluded),
+ *              or NULL for unsalted trees throughout
+ *   d_levels : out, the coset trees back to back (toyni_merkle_total_digests(m_k / 4) x 32 bytes each)
+ *   d_betas  : out (may be NULL), 4 R words: beta of every round, plain canonical (beta^2 is not stored)
+ * Every round writes exactly what toyni_fri_fold4_commit_ext_device writes for its beta.  m0 <= final_size enqueues nothing and
+ * leaves d_tr untouched.  A d_tr whose status is set gives beta = beta^2 = 0 in every round; the layers and trees are still written.
+ * No host in the loop, no callback, no blocking; the context is locked for the enqueue only.  beta reaches a fold through a record
+ * of two factor tables (beta / 2 and beta^2 / 2, the product formed on the device) in the per-stream buffer of 3l, whose layout for
+ * the two-to-one phases is unchanged.  Small rounds run as the same plain chain: the fused tail of 3l is not used here.
+ * Refused before anything is enqueued, the outputs untouched: TOYNI_E_NULL for a null ctx, d_layer0, d_tr, d_layers or d_levels;
+ * TOYNI_E_INVALID_SIZE for an m0 or final_size that is not a power of two, final_size < 4, an odd log2(m0 / final_size), or m0 > n;
+ * TOYNI_E_ZERO_INVERSE for x0 == 0; TOYNI_E_RANGE for x0 >= p or a misaligned pointer. */
+int toyni_fri4_commit_phase_transcript_ext_device(toyni_ntt_ctx* ctx, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size,
+                                                  const uint8_t* d_salts, toyni_transcript* d_tr, uint32_t* d_layers, uint8_t* d_levels,
+                                                  uint32_t* d_betas, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:

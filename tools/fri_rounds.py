@@ -17,7 +17,18 @@ cheaper by the interpreter's share); (new) toyni_fri_commit_phase_transcript[_ex
 1 KiB upload of the initial transcript included.  --tail-log N sets TOYNI_FRI_TAIL_LOG for the process before the first call (the knob
 is read once): -1 is variant (b), every round launched; the default is variant (c), the fused small rounds.  Both sides start from the
 same transcript and must leave the same layers, trees and transcript; they alternate within one process after a warm-up of both.
-With the fused tail a captured graph of the new phase at 2^16 is replayed as well (replay + synchronisation)."""
+With the fused tail a captured graph of the new phase at 2^16 is replayed as well (replay + synchronisation).
+
+--ext --arity4: the four-to-one phase under coset leaves (include/toyni_hip.h 3m, toyni_fri4_commit_phase_transcript_ext_device)
+against the two-to-one phase on the same device transcript (3l, toyni_fri_commit_phase_transcript_ext_device), m0 = 2^12, 2^16 and
+2^20 down to 16, salted, the same layer 0 and x0.  The two are different protocols (other layers, other trees), so there is no output
+to compare: each is held to its own judges by the tests.  Timing: device events around a WINDOW of back-to-back calls on one stream,
+the window sized (from a calibration run) to --window seconds; the two phases alternate window by window within one process, --alternations
+times, the order flipped every time, after a warm-up window of both.  The transcript is loaded once per window (a squeeze leaves a
+32-byte state, so it never grows).  Per phase: the median time per call over the windows, the spread (max - min) / median over the
+windows, and the host's enqueue time per call, which says whether a window was bound by the device or by the launches.  No threshold:
+the expectation written down before the first run is the count of dependent tree levels; the ratio is reported as
+measured, with whether it lies inside the spread."""
 import argparse
 import ctypes
 import os
@@ -298,14 +309,108 @@ def main_transcript(ext, reps, warmup, tail_log):
     return 0
 
 
+# ---- --ext --arity4 ----
+def arity4_case(ctx, log_m0, window_s, alternations):
+    from toyni_amd import prover as pv
+    dev = torch.device("cuda", 0)
+    m0 = 1 << log_m0
+    halves = [m0 >> (k + 1) for k in range(log_m0 - EXT_FINAL.bit_length() + 1)]
+    quarters = [m0 >> (2 * k + 2) for k in range((log_m0 - EXT_FINAL.bit_length() + 1) // 2)]
+    assert halves[-1] == EXT_FINAL and quarters[-1] == EXT_FINAL
+    layer0 = torch.randint(0, P, (4 * m0,), dtype=torch.int32, device=dev)
+    salts = torch.randint(0, 256, (sum(halves[:-1]), 16), dtype=torch.uint8, device=dev)      # the four-to-one phase reads a prefix
+    out2 = (torch.empty(4 * sum(halves), dtype=torch.int32, device=dev),
+            torch.empty((sum(lib.toyni_merkle_total_digests(h) for h in halves), 32), dtype=torch.uint8, device=dev))
+    out4 = (torch.empty(4 * sum(quarters), dtype=torch.int32, device=dev),
+            torch.empty((sum(lib.toyni_merkle_total_digests(q // 4) for q in quarters), 32), dtype=torch.uint8, device=dev))
+    import hashlib
+    state0 = hashlib.sha256(b"toyni-stark-v1").digest() + bytes(range(32))
+    tr = pv.DeviceTranscript()
+    s = torch.cuda.Stream(device=dev)
+
+    def two():
+        pv.fri_commit_phase_transcript_ext_device(ctx, layer0.data_ptr(), m0, EXT_X0, EXT_FINAL, salts.data_ptr(), tr, out2[0].data_ptr(),
+                                                  out2[1].data_ptr(), 0, s.cuda_stream)
+
+    def four():
+        pv.fri4_commit_phase_transcript_ext_device(ctx, layer0.data_ptr(), m0, EXT_X0, EXT_FINAL, salts.data_ptr(), tr, out4[0].data_ptr(),
+                                                   out4[1].data_ptr(), 0, s.cuda_stream)
+
+    def window(f, calls):
+        """(device seconds per call, host enqueue seconds per call) of `calls` back-to-back calls"""
+        tr.load(state0, s.cuda_stream)
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record(s)
+        t0 = time.perf_counter()
+        for _ in range(calls):
+            f()
+        t1 = time.perf_counter()
+        b.record(s)
+        torch.cuda.synchronize()
+        assert tr.status() == 0
+        return a.elapsed_time(b) * 1e-3 / calls, (t1 - t0) / calls
+
+    phases = {"two-to-one": two, "four-to-one": four}
+    calls = {}
+    for name, f in phases.items():          # warm-up and calibration: a short window, then the count that fills window_s
+        window(f, 5)
+        calls[name] = max(5, int(window_s / window(f, 20)[0]) + 1)
+        window(f, calls[name])
+    dev_s, host_s = {n: [] for n in phases}, {n: [] for n in phases}
+    for r in range(alternations):
+        for name in (list(phases) if r % 2 == 0 else list(phases)[::-1]):
+            d, h = window(phases[name], calls[name])
+            dev_s[name].append(d)
+            host_s[name].append(h)
+    tr.free()
+    return len(halves), len(quarters), calls, dev_s, host_s
+
+
+def main_arity4(window_s, alternations):
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from csrc_hash import csrc_sha256
+    ctx = toyni_amd.NttContext(1 << max(EXT_SIZES))
+    print(f"# tools/fri_rounds.py --ext --arity4  Ext FRI commit phase on the device transcript, four-to-one under coset leaves (3m) against "
+          f"two-to-one (3l, TOYNI_FRI_TAIL_LOG={os.environ.get('TOYNI_FRI_TAIL_LOG', 'default')}); final_size {EXT_FINAL}, salted, x0 {EXT_X0}; "
+          f"device events around windows of back-to-back calls sized to {window_s} s, {alternations} alternations, order flipped each time")
+    print(f"# device: {torch.cuda.get_device_name(0)}")
+    print(f"# csrc_sha256: {csrc_sha256()}")
+    print("# expectation written before the first run (a count, not a measurement): dependent tree levels two-to-one / four-to-one")
+    for log_m0 in EXT_SIZES:
+        r2, r4, calls, dev_s, host_s = arity4_case(ctx, log_m0, window_s, alternations)
+        levels2 = sum(log_m0 - k - 1 for k in range(r2))                    # a tree of m / 2 leaves has log2(m) - 1 levels above its leaves
+        levels4 = sum(log_m0 - 2 * k - 4 for k in range(r4))                # a tree of m / 16 leaves has log2(m) - 4
+        print(f"m0 = 2^{log_m0}: {r2} rounds / {levels2} node levels two-to-one, {r4} rounds / {levels4} node levels four-to-one "
+              f"(level ratio {levels2 / max(levels4, 1):.2f}, round ratio {r2 / r4:.2f})")
+        med, spr = {}, {}
+        for name in ("two-to-one", "four-to-one"):
+            v = dev_s[name]
+            med[name], spr[name] = statistics.median(v), (max(v) - min(v)) / statistics.median(v)
+            print(f"  {name:11s}  {med[name] * 1e6:9.1f} us per call (median of {len(v)} windows of {calls[name]} calls, "
+                  f"{med[name] * calls[name]:.2f} s each)   spread {spr[name] * 100:4.1f} %   min {min(v) * 1e6:9.1f}   max {max(v) * 1e6:9.1f}   "
+                  f"host enqueue {statistics.median(host_s[name]) * 1e6:7.1f} us per call")
+        ratio = med["two-to-one"] / med["four-to-one"]
+        inside = abs(ratio - 1.0) <= spr["two-to-one"] + spr["four-to-one"]
+        print(f"  two-to-one / four-to-one = {ratio:.3f}   ({'INSIDE' if inside else 'outside'} the run-to-run spread of the two)")
+    return 0
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--ext", action="store_true", help="the Ext commit phase against the composed sequence (see above)")
     ap.add_argument("--transcript", action="store_true", help="the commit phase on the device transcript against the callback phase (see above)")
     ap.add_argument("--tail-log", type=int, default=None, help="with --transcript: TOYNI_FRI_TAIL_LOG for this process (-1: every round launched)")
+    ap.add_argument("--arity4", action="store_true", help="with --ext: the four-to-one phase under coset leaves against the two-to-one phase (see above)")
+    ap.add_argument("--window", type=float, default=0.3, help="with --arity4: seconds of device time per timed window")
+    ap.add_argument("--alternations", type=int, default=7, help="with --arity4: windows per phase (at least 5)")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
     args = ap.parse_args()
+    if args.arity4:
+        if not args.ext or args.transcript or args.alternations < 5:
+            ap.error("--arity4 goes with --ext alone, and with at least 5 alternations")
+        sys.exit(main_arity4(args.window, args.alternations))
     if args.transcript:
         sys.exit(main_transcript(args.ext, args.reps, args.warmup, args.tail_log))
     sys.exit(main_ext(args.reps, args.warmup) if args.ext else main())

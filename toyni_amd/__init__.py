@@ -15,6 +15,7 @@ from .fri import fri_fold, fri_fold_device, fri_fold_ext, fri_fold_ext_device, f
 from .domain import BabyBearDomain  # noqa: F401
 from .merkle import (MerkleTree, RowMerkleTree, ROWS_COLUMN_MAJOR, ROWS_ROW_MAJOR, merkle_commit_device,  # noqa: F401
                      merkle_commit_rows_device, merkle_open_rows_device)
+from .merkle import CosetExtMerkleTree, merkle_commit_cosets_ext_device, merkle_open_cosets_ext_device  # noqa: F401  (include/toyni_hip.h 3m)
 from . import prover  # noqa: F401
 from .prover import AirBuilder, AirProgram, air_insns, air_quotient_device  # noqa: F401  (include/toyni_hip.h 3f)
 from .prover import air_ext_weights, air_quotient_ext_device  # noqa: F401  (include/toyni_hip.h 3k)

@@ -150,6 +150,13 @@ SIGNATURES = {
                                                          c_void_p, c_void_p]),
     "toyni_fri_commit_phase_transcript_ext_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p,
                                                              c_void_p, c_void_p]),
+    # section 3m
+    "toyni_merkle_commit_cosets_ext_device": (c_int, [c_void_p, c_size, c_void_p, c_void_p, c_void_p]),
+    "toyni_merkle_open_cosets_ext_device": (c_int, [c_void_p, c_size, c_void_p, c_void_p, c_void_p, c_size, c_void_p, c_void_p]),
+    "toyni_fri_fold4_commit_ext_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_void_p, c_u32, c_void_p, c_void_p, c_void_p]),
+    "toyni_fri4_query_positions_device": (c_int, [c_void_p, c_size, c_size, c_size, c_void_p, c_void_p]),
+    "toyni_fri4_commit_phase_transcript_ext_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                              c_void_p, c_void_p]),
     # section 3c
     "toyni_fri_fold_commit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -180,9 +180,21 @@ TOYNI_HD Digest merkle_row_leaf(uint32_t width, const uint32_t* salt_words /* 4 
 //                 multiple of 4, so a quad is inside the row or outside it, and the matrix 16-byte aligned), else word loads
 // Only columns below `width` are addressed: nothing between n and col_stride, nothing past the matrix.
 constexpr int ROWS_COLUMN_MAJOR = 0, ROWS_ROW_MAJOR = 1;
+// Internal, no TOYNI_ROWS_* value of the header: the COSET leaf of an Ext layer (include/toyni_hip.h 3m).  `values` is a layer of
+// 4 col_stride Ext elements (AoS, 16-byte aligned), row i = the elements i, i + col_stride, i + 2 col_stride, i + 3 col_stride -- the
+// four quarters of the layer -- and width = 16: chunk j is the two elements of quarters 2 j and 2 j + 1, two 16-byte loads that
+// consecutive lanes make on consecutive elements.
+constexpr int ROWS_EXT_QUARTERS = 2;
 struct alignas(16) RowQuad { uint32_t x, y, z, w; };
 template <int LAYOUT>
 TOYNI_HD void rows_load_chunk(const uint32_t* values, uint64_t i, uint32_t width, uint64_t col_stride, bool vec, int j, uint32_t (&v)[8]) {
+    if (LAYOUT == ROWS_EXT_QUARTERS) {
+        const RowQuad* p = reinterpret_cast<const RowQuad*>(values) + (i + 2u * (uint64_t)j * col_stride);
+        const RowQuad a = p[0], b = p[col_stride];
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+        v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+        return;
+    }
     const uint32_t c0 = 8u * (uint32_t)j;
     if (LAYOUT == ROWS_COLUMN_MAJOR) {
         const uint32_t* p = values + (uint64_t)c0 * col_stride + i;
@@ -210,6 +222,11 @@ template <int LAYOUT, bool SALTED>
 TOYNI_HD Digest merkle_row_leaf_at(const uint32_t* values, uint64_t i, uint32_t width, uint64_t col_stride, bool vec, const uint32_t* salt_words) {
     return merkle_row_leaf<SALTED>(width, salt_words,
                                    [=](int j, uint32_t (&v)[8]) { rows_load_chunk<LAYOUT>(values, i, width, col_stride, vec, j, v); });
+}
+
+// word c < 16 of coset leaf `index` of an Ext layer of 4 n elements (ROWS_EXT_QUARTERS): what an opening record carries as value c
+TOYNI_HD uint32_t coset_value_word(const uint32_t* layer, uint64_t n, uint64_t index, uint32_t c) {
+    return layer[4u * (index + (uint64_t)(c >> 2) * n) + (c & 3u)];
 }
 
 // node = SHA256(01 || left || right): 65 bytes, two blocks

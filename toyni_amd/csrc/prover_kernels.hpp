@@ -1201,6 +1201,60 @@ TOYNI_HD FoldExtLeaf fold_ext_commit_one(const Ext4& a, const Ext4& b, uint32_t 
     return r;
 }
 
+// ---- one LEAF of a four-to-one Ext FRI round that commits what it folds (include/toyni_hip.h 3m) ----
+// The folded layer L'' (m / 4 elements) is committed under coset leaves: leaf t < m / 16 holds L''[t + q m/16], q = 0 .. 3, and
+//   L''[j] = fold( fold(L[j], L[j + m/2]; s, beta), fold(L[j + m/4], L[j + 3m/4]; s / I, beta); s^2, beta^2 ),  s = 1 / (x0 w_m^j),
+// I = w_m^(m/4) = w_4: the two pairwise rounds of fri_fold_ext on the points x0 w_m^i and x0^2 w_(m/2)^i, in registers.
+//   in[q + 4 r] = L[t + q m/16 + r m/4]       the 16 elements one leaf depends on (stride m / 16 in memory)
+//   sR[q]       = Montgomery form of 1 / (x0 w_m^(t + q m/16))
+//   iinvR       = Montgomery form of 1 / w_4
+//   f1, f2      = ExtFactor of beta / 2 and of beta^2 / 2
+// 12 fold_ext_one; then the coset leaf 00 || salt(16) || four Ext::to_bytes: the row leaf of width 16, three SHA-256 blocks either
+// way, hashed from the 16 folded words.  Every array index is a constant: the chunk loader below selects, it does not index.
+// What fri_fold4_ext_commit_kernel runs per thread, and what tests/emu steps on the CPU.
+struct Fold4ExtLeaf { Ext4 folded[4]; Digest leaf; };
+template <bool SALTED>
+TOYNI_HD Fold4ExtLeaf fold4_ext_commit_leaf(const Ext4 (&in)[16], const uint32_t (&sR)[4], uint32_t iinvR, const ExtFactor& f1, const ExtFactor& f2,
+                                            const uint32_t* salt_words) {
+    Fold4ExtLeaf r;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const Ext4 u = fold_ext_one(in[q], in[q + 8], sR[q], f1);
+        const Ext4 v = fold_ext_one(in[q + 4], in[q + 12], mont_mul(sR[q], iinvR), f1);
+        r.folded[q] = fold_ext_one(u, v, mont_mul(sR[q], sR[q]), f2);
+    }
+    const Ext4 e0 = r.folded[0], e1 = r.folded[1], e2 = r.folded[2], e3 = r.folded[3];
+    r.leaf = merkle_row_leaf<SALTED>(16u, salt_words, [&](int j, uint32_t (&c)[8]) {   // chunk 0: elements 0 and 1; chunk 1: 2 and 3
+        const Ext4& lo = j == 0 ? e0 : e2;
+        const Ext4& hi = j == 0 ? e1 : e3;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) { c[k] = lo.c[k]; c[4 + k] = hi.c[k]; }
+    });
+    return r;
+}
+
+// The record a round of the four-to-one phase leaves for the next fold: two ExtFactors, of beta / 2 and of beta^2 / 2 (16 words).
+// beta: plain canonical coordinates; half_r2 / half11_r2 = (1 / 2) R^2 and (11 / 2) R^2 as in the two-to-one phase, eleven_r2 =
+// 11 R^2.  beta^2 is ONE Ext product of the canonical beta by its own factor table (Montgomery forms of beta and 11 beta).
+TOYNI_HD void fri4_round_record(const uint32_t (&beta)[4], uint32_t half_r2, uint32_t half11_r2, uint32_t eleven_r2, ExtFactor (&rec)[2]) {
+    ExtFactor fb;
+    Ext4 b;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        b.c[k] = beta[k];
+        fb.b[k] = mont_mul(beta[k], BB_R2);
+        fb.b11[k] = mont_mul(beta[k], eleven_r2);
+        rec[0].b[k] = mont_mul(beta[k], half_r2);
+        rec[0].b11[k] = mont_mul(beta[k], half11_r2);
+    }
+    const Ext4 sq = ext_mul(b, fb);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        rec[1].b[k] = mont_mul(sq.c[k], half_r2);
+        rec[1].b11[k] = mont_mul(sq.c[k], half11_r2);
+    }
+}
+
 // ---- Merkle openings (src/merkle.rs:50-80, src/fibonacci.rs:366-375) ----
 // record of one opening: depth x 32 path bytes | 16 salt bytes (zero when unsalted) | value as 8 LE bytes | depth position bytes
 // (1 = the sibling is the LEFT input of the node hash), padding zero to a multiple of 8

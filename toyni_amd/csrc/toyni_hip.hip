@@ -1721,6 +1721,141 @@ __global__ void __launch_bounds__(256) fri_fold_ext_commit_rec_kernel(const Fold
     }
 }
 
+// ---- four-to-one Ext FRI rounds under coset leaves (include/toyni_hip.h 3m) ----
+// One thread per LEAF of the folded layer (fold4_ext_commit_leaf, prover_kernels.hpp): the 16 input elements t + k m/16, k < 16 --
+// sixteen 16-byte loads, each one consecutive across the lanes of a wave --, 12 pairwise folds, the four outputs t + q m/16 and the
+// three compressions of the leaf from the folded words in registers.  No LDS, no barrier.  Hash-bound (three compressions against
+// about a third of one in folding), so the wide grid-stride shape of fri_fold_ext_commit_kernel and never a stream shape.  The four
+// outputs of a leaf are m / 16 apart: a mapping with one output per lane could not hash the leaf without an exchange.
+struct Fold4ExtArgs {
+    const uint32_t* evals;   // m Ext elements
+    uint32_t* out;           // m / 4 Ext elements
+    SubDomain dom;           // winv_N^(i << s) for i < m (Montgomery)
+    uint32_t xinvR;          // Montgomery form of x0^-1
+    uint32_t iinvR;          // Montgomery form of w_4^-1
+    uint64_t leaves;         // m / 16
+};
+template <bool SALTED>
+__device__ __forceinline__ void fold4_ext_commit_sweep(const Fold4ExtArgs& a, const ExtFactor& f1, const ExtFactor& f2, const uint4* __restrict__ salts,
+                                                       Digest* __restrict__ leaves) {
+    const uint64_t nl = a.leaves;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint4* e = reinterpret_cast<const uint4*>(a.evals);
+    uint4* o = reinterpret_cast<uint4*>(a.out);
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nl; t += stride) {
+        Ext4 in[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const uint4 v = e[t + (uint64_t)k * nl];
+            in[k] = Ext4{{v.x, v.y, v.z, v.w}};
+        }
+        uint32_t sR[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) sR[q] = mont_mul(subdomain_mont(a.dom, (uint32_t)(t + (uint64_t)q * nl)), a.xinvR);
+        uint32_t sw[4] = {0u, 0u, 0u, 0u};
+        if constexpr (SALTED) {
+            const uint4 s = salts[t];
+            sw[0] = s.x; sw[1] = s.y; sw[2] = s.z; sw[3] = s.w;
+        }
+        const Fold4ExtLeaf r = fold4_ext_commit_leaf<SALTED>(in, sR, a.iinvR, f1, f2, sw);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) o[t + (uint64_t)q * nl] = make_uint4(r.folded[q].c[0], r.folded[q].c[1], r.folded[q].c[2], r.folded[q].c[3]);
+        leaves[t] = r.leaf;
+    }
+}
+struct Fold4ExtFactors { ExtFactor beta_half, beta2_half; };
+template <bool SALTED>
+__global__ void __launch_bounds__(256) fri_fold4_ext_commit_kernel(const Fold4ExtArgs a, const Fold4ExtFactors f, const uint4* __restrict__ salts,
+                                                                   Digest* __restrict__ leaves) {
+    fold4_ext_commit_sweep<SALTED>(a, f.beta_half, f.beta2_half, salts, leaves);
+}
+// its twin for the phase on a device transcript: the two factors from the record fri4_transcript_round_kernel left
+template <bool SALTED>
+__global__ void __launch_bounds__(256) fri_fold4_ext_commit_rec_kernel(const Fold4ExtArgs a, const Fold4ExtFactors* __restrict__ rec,
+                                                                       const uint4* __restrict__ salts, Digest* __restrict__ leaves) {
+    const Fold4ExtFactors f = *rec;
+    fold4_ext_commit_sweep<SALTED>(a, f.beta_half, f.beta2_half, salts, leaves);
+}
+
+// Between two rounds of that phase, one wave: fri_transcript_round_kernel with an Ext beta and a record of TWO factors
+// (fri4_round_record: beta / 2 and beta^2 / 2).  The five dependent compressions and the one Ext product run on lane 0.
+__global__ void __launch_bounds__(TRANSCRIPT_T) fri4_transcript_round_kernel(TranscriptState* __restrict__ tr, const uint8_t* __restrict__ root,
+                                                                              uint32_t squeeze, uint32_t half_r2, uint32_t half11_r2, uint32_t eleven_r2,
+                                                                              uint32_t* __restrict__ rec, uint32_t* __restrict__ betas) {
+    if (threadIdx.x != 0) return;
+    if (root) transcript_absorb(*tr, root, 32u);
+    if (squeeze == 0u) return;
+    uint32_t beta[4];
+    transcript_squeeze(*tr, beta, 4u);
+    ExtFactor f[2];
+    fri4_round_record(beta, half_r2, half11_r2, eleven_r2, f);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (betas) betas[k] = beta[k];
+        rec[k] = f[0].b[k]; rec[4 + k] = f[0].b11[k];
+        rec[8 + k] = f[1].b[k]; rec[12 + k] = f[1].b11[k];
+    }
+}
+
+// Coset leaves of a layer as it lies: merkle_row_leaf_at with the internal layout ROWS_EXT_QUARTERS (merkle_kernels.hpp), width 16,
+// one thread per leaf in the launch shape of merkle_rows_leaf_kernel.  n = m / 4 leaves.
+template <bool SALTED>
+__global__ void __launch_bounds__(256) merkle_coset_leaf_kernel(const uint32_t* __restrict__ layer, const uint4* __restrict__ salts,
+                                                                Digest* __restrict__ out, size_t n) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        uint32_t sw[4] = {0u, 0u, 0u, 0u};
+        if constexpr (SALTED) {
+            const uint4 s = salts[i];
+            sw[0] = s.x; sw[1] = s.y; sw[2] = s.z; sw[3] = s.w;
+        }
+        out[i] = merkle_row_leaf_at<ROWS_EXT_QUARTERS, SALTED>(layer, i, 16u, n, true, sw);
+    }
+}
+
+// list k < rounds of `count` words: the leaf query q opens in layer k, d_indices[q] mod (m0 >> (2 k + 2))
+__global__ void __launch_bounds__(256) fri4_query_positions_kernel(const uint32_t* __restrict__ indices, uint32_t count, uint64_t m0, uint64_t total,
+                                                                   uint32_t* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) {
+        const uint64_t k = t / count, leaves = m0 >> (2u * k + 2u);
+        out[t] = (uint32_t)(indices[t % count] & (leaves - 1u));
+    }
+}
+
+// Openings of coset leaves: merkle_open_rows_kernel's record with width 16, the 16 value words of leaf `index` gathered from the four
+// quarters of the layer (word c of the leaf = word c mod 4 of element index + (c / 4) n, n = m / 4 leaves).
+__global__ void __launch_bounds__(256) merkle_open_cosets_kernel(const OpenRows g) {
+    const uint32_t depth = merkle_depth(g.n);
+    const uint64_t values_at = (uint64_t)depth * 32u + 16u, flags_at = values_at + 8u * 16u;
+    const uint64_t rec = flags_at + ((depth + 7u) & ~7u);
+    const uint64_t per = (uint64_t)depth + 1u + 16u, total = (uint64_t)g.nidx * per;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t w = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; w < total; w += stride) {
+        const uint32_t k = (uint32_t)(w / per);
+        const uint64_t item = w % per;
+        const uint64_t index = g.indices[k];
+        uint8_t* r = g.out + (uint64_t)k * rec;
+        if (item < depth) {
+            bool is_left;
+            const uint64_t row = merkle_sibling_row(g.n, index, (uint32_t)item, is_left);
+            reinterpret_cast<Digest*>(r)[item] = g.levels[row];
+            r[flags_at + item] = is_left ? 1 : 0;
+        } else if (item == depth) {
+            uint32_t* tail = reinterpret_cast<uint32_t*>(r + (uint64_t)depth * 32u);
+            uint4 sv = make_uint4(0u, 0u, 0u, 0u);
+            if (g.salts) sv = g.salts[index];
+            tail[0] = sv.x; tail[1] = sv.y; tail[2] = sv.z; tail[3] = sv.w;
+            for (uint64_t b = flags_at + depth; b < rec; ++b) r[b] = 0;   // byte stores, clear of the position bytes
+        } else {
+            const uint64_t c = item - depth - 1u;
+            uint32_t* val = reinterpret_cast<uint32_t*>(r + values_at + 8u * c);
+            val[0] = coset_value_word(g.values, g.n, index, (uint32_t)c);
+            val[1] = 0u;
+        }
+    }
+}
+
 // ALL remaining rounds of a transcript commit phase in ONE workgroup, from the first round whose folded layer has at most MERKLE_TAIL
 // leaves: a round that small is a chain of dependent compressions in which every launch boundary costs about what the hash it
 // separates does, and with beta produced on the device nothing between two rounds needs the host.  The layer (folded in place: thread
@@ -3750,6 +3885,167 @@ int toyni_fri_commit_phase_transcript_ext_device(toyni_ntt_ctx* c, const uint32_
     if (m0 > c->n) return TOYNI_E_INVALID_SIZE;
     if (m0 <= final_size) return TOYNI_OK;
     return commit_phase_transcript(c, d_layer0, m0, x0, final_size, 4, d_salts, d_tr, d_layers, d_levels, d_betas, (hipStream_t)stream);
+}
+
+// ---- four-to-one Ext FRI rounds under coset leaves (include/toyni_hip.h 3m) ----
+int toyni_merkle_commit_cosets_ext_device(const uint32_t* d_layer, size_t m, const uint8_t* d_salts, uint8_t* d_levels, void* stream) {
+    if (!d_layer || !d_levels) return TOYNI_E_NULL;
+    if (m == 0) return TOYNI_OK;
+    if (!is_pow2(m) || m < 4) return TOYNI_E_INVALID_SIZE;
+    if (m > ((size_t)1 << 33) || (((uintptr_t)d_layer | (uintptr_t)d_levels | (uintptr_t)d_salts) & 15)) return TOYNI_E_RANGE;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = m / 4;
+    const uint4* salts = reinterpret_cast<const uint4*>(d_salts);
+    Digest* out = reinterpret_cast<Digest*>(d_levels);
+    const dim3 grid(grid_for(n)), block(256);
+    if (salts) hipLaunchKernelGGL((merkle_coset_leaf_kernel<true>), grid, block, 0, s, d_layer, salts, out, n);
+    else hipLaunchKernelGGL((merkle_coset_leaf_kernel<false>), grid, block, 0, s, d_layer, salts, out, n);
+    return enqueue_merkle_upper(d_levels, n, s);
+}
+
+int toyni_merkle_open_cosets_ext_device(const uint8_t* d_levels, size_t m, const uint32_t* d_layer, const uint8_t* d_salts, const uint32_t* d_indices,
+                                        size_t nidx, uint8_t* d_out, void* stream) {
+    if (!d_levels || !d_layer || !d_indices || !d_out) return TOYNI_E_NULL;
+    if (m == 0) return TOYNI_OK;
+    if (!is_pow2(m) || m < 4) return TOYNI_E_INVALID_SIZE;
+    if (m > ((size_t)1 << 33) || nidx > 0xFFFFFFFFull || (((uintptr_t)d_levels | (uintptr_t)d_layer | (uintptr_t)d_salts) & 15) ||
+        ((uintptr_t)d_out & 7) || ((uintptr_t)d_indices & 3)) return TOYNI_E_RANGE;
+    if (nidx == 0) return TOYNI_OK;
+    const size_t n = m / 4;
+    const uint64_t work = (uint64_t)nidx * (merkle_depth(n) + 1 + 16);
+    const OpenRows g{reinterpret_cast<const Digest*>(d_levels), (uint64_t)n, d_layer, 16u, ROWS_EXT_QUARTERS, (uint64_t)n,
+                     reinterpret_cast<const uint4*>(d_salts), d_indices, (uint32_t)nidx, d_out};
+    hipLaunchKernelGGL(merkle_open_cosets_kernel, dim3(grid_for(work)), dim3(256), 0, (hipStream_t)stream, g);
+    return (int)hipGetLastError();
+}
+
+// beta^2 / 2 on the host (src/ext.rs:178-192), for the call that is handed beta
+static ExtFactor ext_square_half_host(const uint32_t b[4]) {
+    const auto mul = bb_mul_host;
+    const auto add = [](uint32_t x, uint32_t y) { return (uint32_t)(((uint64_t)x + y) % BB_P); };
+    uint32_t sq[4];
+    sq[0] = add(mul(b[0], b[0]), mul(11u, add(add(mul(b[1], b[3]), mul(b[2], b[2])), mul(b[3], b[1]))));
+    sq[1] = add(add(mul(b[0], b[1]), mul(b[1], b[0])), mul(11u, add(mul(b[2], b[3]), mul(b[3], b[2]))));
+    sq[2] = add(add(mul(b[0], b[2]), mul(b[1], b[1])), add(mul(b[2], b[0]), mul(11u, mul(b[3], b[3]))));
+    sq[3] = add(add(mul(b[0], b[3]), mul(b[1], b[2])), add(mul(b[2], b[1]), mul(b[3], b[0])));
+    ExtFactor f{};
+    ext_beta_half(sq, &f);
+    return f;
+}
+
+// Arguments checked by the caller: m >= 16 a power of two <= n, x in [1, p).
+static Fold4ExtArgs fold4_args(toyni_ntt_ctx* c, const uint32_t* d_evals, uint32_t* d_out, size_t m, uint32_t x) {
+    Fold4ExtArgs a{};
+    a.evals = d_evals;
+    a.out = d_out;
+    a.dom = sub_domain(c->plan, c->d_inv, c->plan.log_n - ilog2(m));
+    a.xinvR = to_mont_host(bb_inv_host(x));
+    a.iinvR = to_mont_host(bb_inv_host(bb_root_of_unity_host(2)));
+    a.leaves = m / 16;
+    return a;
+}
+
+int toyni_fri_fold4_commit_ext_device(toyni_ntt_ctx* c, const uint32_t* d_evals, uint32_t* d_out, size_t m, const uint32_t beta[4], uint32_t x0,
+                                      const uint8_t* d_salts, uint8_t* d_levels, void* stream) {
+    // every refusal that the arguments alone decide comes before the context is read
+    if (!c || !d_evals || !d_out || !beta || !d_levels) return TOYNI_E_NULL;
+    if (m && (!is_pow2(m) || m < 16)) return TOYNI_E_RANGE;
+    if (x0 == 0) return TOYNI_E_ZERO_INVERSE;
+    if (((uintptr_t)d_evals | (uintptr_t)d_out | (uintptr_t)d_levels | (uintptr_t)d_salts) & 15) return TOYNI_E_RANGE;   // 16-byte accesses
+    Fold4ExtFactors f{};
+    if (x0 >= BB_P || !ext_beta_half(beta, &f.beta_half)) return TOYNI_E_RANGE;
+    f.beta2_half = ext_square_half_host(beta);
+    if (m == 0) return TOYNI_OK;
+    if (m > c->n) return TOYNI_E_RANGE;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    const Fold4ExtArgs a = fold4_args(c, d_evals, d_out, m, x0);
+    const dim3 grid(grid_for(a.leaves)), block(256);
+    Digest* leaves = reinterpret_cast<Digest*>(d_levels);
+    if (d_salts) hipLaunchKernelGGL((fri_fold4_ext_commit_kernel<true>), grid, block, 0, s, a, f, reinterpret_cast<const uint4*>(d_salts), leaves);
+    else hipLaunchKernelGGL((fri_fold4_ext_commit_kernel<false>), grid, block, 0, s, a, f, static_cast<const uint4*>(nullptr), leaves);
+    return enqueue_merkle_upper(d_levels, a.leaves, s);
+}
+
+// log2(m0 / final_size) / 2 for sizes the four-to-one calls accept, -1 otherwise (both powers of two, final_size >= 4, an even ratio)
+static int fri4_rounds(size_t m0, size_t final_size) {
+    if (!is_pow2(m0) || !is_pow2(final_size) || final_size < 4) return -1;
+    if (m0 <= final_size) return 0;
+    const int d = ilog2(m0) - ilog2(final_size);
+    return d % 2 ? -1 : d / 2;
+}
+
+int toyni_fri4_query_positions_device(const uint32_t* d_indices, size_t count, size_t m0, size_t final_size, uint32_t* d_out, void* stream) {
+    if (!d_indices || !d_out) return TOYNI_E_NULL;
+    if (((uintptr_t)d_indices & 3) || ((uintptr_t)d_out & 3)) return TOYNI_E_RANGE;
+    if (!is_pow2(m0) || !is_pow2(final_size) || final_size < 1 || (uint64_t)m0 > ((uint64_t)1 << 32) || count > 65536) return TOYNI_E_RANGE;
+    const int rounds = fri4_rounds(m0, final_size);
+    if (rounds < 0) return TOYNI_E_INVALID_SIZE;
+    if (count == 0 || rounds == 0) return TOYNI_OK;
+    const uint64_t total = (uint64_t)rounds * count;
+    hipLaunchKernelGGL(fri4_query_positions_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, d_indices, (uint32_t)count, (uint64_t)m0,
+                       total, d_out);
+    return (int)hipGetLastError();
+}
+
+// The phase: the chain of commit_phase_transcript with half the rounds and no fused tail -- per round the fold (its record written by
+// the one-wave kernel that closed the round before, or opened the phase), the node levels, that kernel again.  A record is 16 words:
+// at most 13 rounds (2^27 down to 4) fit the FRI_REC_WORDS buffer of the stream.
+static_assert(13 * sizeof(Fold4ExtFactors) <= FRI_REC_WORDS * sizeof(uint32_t), "the four-to-one records fit the stream's record buffer");
+int toyni_fri4_commit_phase_transcript_ext_device(toyni_ntt_ctx* c, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size,
+                                                  const uint8_t* d_salts, toyni_transcript* d_tr, uint32_t* d_layers, uint8_t* d_levels,
+                                                  uint32_t* d_betas, void* stream) {
+    if (!c || !d_layer0 || !d_tr || !d_layers || !d_levels) return TOYNI_E_NULL;
+    if (fri4_rounds(m0, final_size) < 0) return TOYNI_E_INVALID_SIZE;
+    if (x0 == 0) return TOYNI_E_ZERO_INVERSE;
+    if (x0 >= BB_P) return TOYNI_E_RANGE;
+    if ((((uintptr_t)d_layer0 | (uintptr_t)d_layers | (uintptr_t)d_levels | (uintptr_t)d_salts | (uintptr_t)d_tr) & 15) || ((uintptr_t)d_betas & 3))
+        return TOYNI_E_RANGE;
+    if (m0 > c->n) return TOYNI_E_INVALID_SIZE;
+    if (m0 <= final_size) return TOYNI_OK;
+    hipStream_t s = (hipStream_t)stream;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    if (int rc = grow(c, s, (void**)&sc.d_fri_rec, &sc.fri_rec_words, FRI_REC_WORDS, sizeof(uint32_t))) return rc;
+    TranscriptState* tr = transcript_of(d_tr);
+    const uint32_t half_r2 = to_mont_host(to_mont_host(BB_HALF)), half11_r2 = to_mont_host(to_mont_host(bb_mul_host(BB_HALF, 11u)));
+    const uint32_t eleven_r2 = to_mont_host(to_mont_host(11u));
+    const uint32_t* cur = d_layer0;
+    uint32_t* out = d_layers;
+    uint8_t* levels = d_levels;
+    const uint8_t* salts = d_salts;
+    uint32_t* betas = d_betas;
+    uint32_t x = x0;
+    uint32_t* rec = sc.d_fri_rec;
+    hipLaunchKernelGGL(fri4_transcript_round_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, s, tr, static_cast<const uint8_t*>(nullptr), 1u, half_r2, half11_r2,
+                       eleven_r2, rec, betas);
+    for (size_t m = m0; m > final_size; m >>= 2) {
+        const size_t quarter = m >> 2;
+        const bool last = quarter == final_size;
+        const Fold4ExtArgs a = fold4_args(c, cur, out, m, x);
+        const size_t digests = toyni_merkle_total_digests(a.leaves);
+        const uint4* round_salts = reinterpret_cast<const uint4*>(last ? nullptr : salts);
+        Digest* leaves = reinterpret_cast<Digest*>(levels);
+        const Fold4ExtFactors* r = reinterpret_cast<const Fold4ExtFactors*>(rec);
+        const dim3 grid(grid_for(a.leaves)), block(256);
+        if (round_salts) hipLaunchKernelGGL((fri_fold4_ext_commit_rec_kernel<true>), grid, block, 0, s, a, r, round_salts, leaves);
+        else hipLaunchKernelGGL((fri_fold4_ext_commit_rec_kernel<false>), grid, block, 0, s, a, r, round_salts, leaves);
+        if (int rc = enqueue_merkle_upper(levels, a.leaves, s)) return rc;
+        const uint8_t* root = levels + (digests - 1) * 32;
+        cur = out;
+        out += quarter * 4;
+        levels += digests * 32;
+        if (salts && !last) salts += a.leaves * 16;
+        if (betas) betas += 4;
+        x = bb_mul_host(x, x);
+        x = bb_mul_host(x, x);   // x^4: the domain of the next layer
+        rec += sizeof(Fold4ExtFactors) / sizeof(uint32_t);
+        hipLaunchKernelGGL(fri4_transcript_round_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, s, tr, root, last ? 0u : 1u, half_r2, half11_r2, eleven_r2, rec,
+                           betas);
+    }
+    return (int)hipGetLastError();
 }
 
 static DomainArgs domain_args(toyni_ntt_ctx* c, unsigned log_m, uint32_t shift) {

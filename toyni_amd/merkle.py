@@ -107,3 +107,55 @@ def merkle_open_rows_device(d_levels: int, n: int, d_values: int, width: int, la
     """nidx opening records of toyni_merkle_open_rows_record_bytes(n, width) bytes each, gathered on the device into d_out."""
     check(lib.toyni_merkle_open_rows_device(d_levels, n, d_values, width, layout, col_stride, d_salts or None, d_indices, nidx, d_out,
                                             stream or None), "GPU Merkle row opening failed")
+
+
+# ---- coset leaves of an Ext FRI layer (include/toyni_hip.h 3m) ----
+def coset_rows(layer4) -> np.ndarray:
+    """(m, 4) Ext elements -> the (m / 4, 16) matrix whose row j is elements j, j + m/4, j + m/2, j + 3m/4: the rows the coset
+    tree commits."""
+    e = np.ascontiguousarray(layer4).reshape(-1, 4)
+    m = e.shape[0]
+    assert m >= 4 and m & (m - 1) == 0, "a layer of a power of two >= 4 Ext elements"
+    return np.ascontiguousarray(e.reshape(4, m // 4, 4).transpose(1, 0, 2)).reshape(m // 4, 16)
+
+
+class CosetExtMerkleTree:
+    """The coset tree of an Ext layer in hashlib, no device: leaf j = [salt_j (16)] || to_bytes of elements j, j + m/4, j + m/2,
+    j + 3m/4; node = sha256(01 || left || right), an odd level pairs its last node with itself (src/merkle.rs:25-48).  What
+    merkle_commit_cosets_ext_device writes, as `levels` (lists of 32-byte digests), `flat()` (the device layout) and `root()`."""
+
+    def __init__(self, layer4, salts=None):
+        import hashlib
+        rows = coset_rows(np.ascontiguousarray(layer4, dtype=np.uint64) % np.uint64(2013265921))
+        n = rows.shape[0]
+        body = rows.astype("<u8").view(np.uint8).reshape(n, 128)
+        if salts is not None:
+            body = np.concatenate([np.ascontiguousarray(salts, dtype=np.uint8).reshape(n, 16), body], axis=1)
+        self.n = n
+        self._leaves = [r.tobytes() for r in body]
+        level = [hashlib.sha256(b"\x00" + l).digest() for l in self._leaves]
+        self.levels = [level]
+        while len(level) > 1:
+            level = [hashlib.sha256(b"\x01" + level[i] + level[i + 1 if i + 1 < len(level) else i]).digest() for i in range(0, len(level), 2)]
+            self.levels.append(level)
+
+    def root(self) -> bytes:
+        return self.levels[-1][0]
+
+    def leaf_bytes(self, index: int) -> bytes:
+        return self._leaves[index]
+
+    def flat(self) -> np.ndarray:
+        return np.frombuffer(b"".join(d for level in self.levels for d in level), dtype=np.uint8).reshape(-1, 32)
+
+
+def merkle_commit_cosets_ext_device(d_layer: int, m: int, d_salts: int, d_levels: int, stream: int = 0) -> None:
+    """The coset tree (m / 4 leaves) of a device-resident layer of m Ext elements, read as it lies; all levels to d_levels."""
+    check(lib.toyni_merkle_commit_cosets_ext_device(d_layer, m, d_salts or None, d_levels, stream or None), "GPU coset commit failed")
+
+
+def merkle_open_cosets_ext_device(d_levels: int, m: int, d_layer: int, d_salts: int, d_indices: int, nidx: int, d_out: int,
+                                  stream: int = 0) -> None:
+    """nidx opening records of toyni_merkle_open_rows_record_bytes(m / 4, 16) bytes each, of the coset leaves d_indices names."""
+    check(lib.toyni_merkle_open_cosets_ext_device(d_levels, m, d_layer, d_salts or None, d_indices, nidx, d_out, stream or None),
+          "GPU coset opening failed")

@@ -578,6 +578,31 @@ def fri_commit_phase_transcript_ext_device(ctx, d_layer0: int, m0: int, x0: int,
           "GPU Ext FRI commit phase (device transcript) failed")
 
 
+# ---- four-to-one Ext FRI rounds under coset leaves (include/toyni_hip.h 3m) ----
+def fri_fold4_commit_ext_device(ctx, d_evals: int, d_out: int, m: int, beta4, x0: int, d_salts: int, d_levels: int, stream: int = 0) -> None:
+    """One four-to-one round: the m / 4 folded Ext elements to d_out (two pairwise folds, beta4 on x0 then beta4^2 on x0^2, in one
+    sweep) and their coset tree (m / 16 leaves, every level) to d_levels."""
+    b = np.ascontiguousarray(beta4, dtype=np.uint32)
+    assert b.size == 4
+    check(lib.toyni_fri_fold4_commit_ext_device(ctx.handle, d_evals, d_out, m, b.ctypes.data, x0, d_salts or None, d_levels, stream or None),
+          "GPU four-to-one fold + commit (Ext) failed")
+
+
+def fri4_query_positions_device(d_indices: int, count: int, m0: int, final_size: int, d_out: int, stream: int = 0) -> None:
+    """The coset leaf `count` queries open in every layer but the final one: list k holds index mod (m0 >> (2 k + 2)), the lists back
+    to back -- rounds x count words."""
+    check(lib.toyni_fri4_query_positions_device(d_indices, count, m0, final_size, d_out, stream or None), "GPU four-to-one query positions failed")
+
+
+def fri4_commit_phase_transcript_ext_device(ctx, d_layer0: int, m0: int, x0: int, final_size: int, d_salts: int, transcript: DeviceTranscript,
+                                            d_layers: int, d_levels: int, d_betas: int = 0, stream: int = 0) -> None:
+    """The Ext commit phase on a device transcript folding four to one per round under coset leaves: half the rounds of
+    fri_commit_phase_transcript_ext_device, each tree two levels lower.  d_betas (optional): four words per round."""
+    check(lib.toyni_fri4_commit_phase_transcript_ext_device(ctx.handle, d_layer0, m0, x0, final_size, d_salts or None, transcript.ptr, d_layers,
+                                                            d_levels, d_betas or None, stream or None),
+          "GPU four-to-one Ext FRI commit phase failed")
+
+
 def merkle_open_record_bytes(n: int) -> int:
     return lib.toyni_merkle_open_record_bytes(n)
 
