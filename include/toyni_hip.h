@@ -760,6 +760,37 @@ int toyni_fri4_commit_phase_transcript_ext_device(toyni_ntt_ctx* ctx, const uint
                                                   uint32_t* d_betas, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * 3n. A proof-of-work nonce ("grinding") on the device transcript of 3l: the step between the last absorbed root and
+ *     toyni_transcript_squeeze_indices_device.  It buys `bits` bits of soundness that would otherwise be paid in queries, without the
+ *     transcript leaving the device.  The protocol is this library's own (the reference has no grinding).  For a transcript whose
+ *     state is the bytes S and a 64-bit nonce:
+ *         accept(S, nonce, bits)  <=>  the first `bits` bits of SHA256(S || LE64(nonce)) are zero, the most significant bit of digest
+ *                                      byte 0 first; 0 <= bits <= 32; bits = 0 accepts every nonce
+ *         grind(S, bits, start, log_tries) = the SMALLEST nonce of [start, start + 2^log_tries) that is accepted
+ *     and the transcript then absorbs the 8 bytes LE64(nonce), exactly as toyni_transcript_absorb_device would.  The answer is a
+ *     function of the arguments alone: never of the grid, the schedule or the run.  A verifier recomputes one hash
+ *     (toyni_pow_check_host), checks it and absorbs the same 8 bytes.  bits = 0 still absorbs a nonce (the value `start`).
+ * ---------------------------------------------------------------------------------------------- */
+#define TOYNI_POW_MAX_BITS 32
+#define TOYNI_POW_MAX_LOG_TRIES 40
+/* Asynchronous on `stream`: one linear chain of three launches (arm, one wave; search, up to 768 workgroups; finish, one wave), no
+ * context, no allocation, no callback, no host read, no environment variable; it can be captured into a graph like its siblings.
+ * d_nonce: one word of device memory, 8-byte aligned -- the result and the only scratch the call needs.  Afterwards *d_nonce holds
+ * the nonce and d_tr is S || LE64(nonce).  What the host cannot see goes into the sticky `status` by 3l's rules; in each of these
+ * cases the transcript's bytes and length stay as they are and *d_nonce = 0: a d_tr whose status is already set; a state with
+ * len + 8 > TOYNI_TRANSCRIPT_CAPACITY (sets TOYNI_E_RANGE); a window without an accepted nonce (sets TOYNI_E_RANGE).  The work is
+ * bounded by the window: no thread tests more than 2^log_tries / (number of threads) candidates, rounded up.
+ * Refused on the host before anything is enqueued, the outputs untouched: TOYNI_E_NULL for a null d_tr or d_nonce; TOYNI_E_RANGE for
+ * a d_tr that is not 16-byte or a d_nonce that is not 8-byte aligned, bits > TOYNI_POW_MAX_BITS, log_tries > TOYNI_POW_MAX_LOG_TRIES,
+ * or a start + 2^log_tries that exceeds 2^64. */
+int toyni_transcript_grind_device(toyni_transcript* d_tr, unsigned bits, uint64_t start, unsigned log_tries, uint64_t* d_nonce,
+                                  void* stream);
+/* accept(state[0 .. len), nonce, bits) on the host: plain host code, no device.  *accepted = 1 or 0.  TOYNI_E_NULL for a null
+ * `accepted` or a null `state` with len > 0 (state may be null when len == 0); TOYNI_E_RANGE for bits > TOYNI_POW_MAX_BITS, with
+ * *accepted untouched.  `len` is not bounded by the transcript's capacity. */
+int toyni_pow_check_host(const uint8_t* state, size_t len, uint64_t nonce, unsigned bits, int* accepted);
+
+/* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:
  *     src/fibonacci.rs:133-150,186-198,222-245, src/math/polynomial.rs:134-144, src/merkle.rs:50-80).  All asynchronous on
  *     `stream`; packed u32 device data; ctx = a context of size N = the LDE size (its domain table supplies x_i = shift w_N^i).

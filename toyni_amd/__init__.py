@@ -19,5 +19,6 @@ from .merkle import CosetExtMerkleTree, merkle_commit_cosets_ext_device, merkle_
 from . import prover  # noqa: F401
 from .prover import AirBuilder, AirProgram, air_insns, air_quotient_device  # noqa: F401  (include/toyni_hip.h 3f)
 from .prover import air_ext_weights, air_quotient_ext_device  # noqa: F401  (include/toyni_hip.h 3k)
+from .prover import pow_check  # noqa: F401  (include/toyni_hip.h 3n)
 
 P = 2013265921

@@ -157,6 +157,9 @@ SIGNATURES = {
     "toyni_fri4_query_positions_device": (c_int, [c_void_p, c_size, c_size, c_size, c_void_p, c_void_p]),
     "toyni_fri4_commit_phase_transcript_ext_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p,
                                                               c_void_p, c_void_p]),
+    # section 3n
+    "toyni_transcript_grind_device": (c_int, [c_void_p, ctypes.c_uint, c_u64, ctypes.c_uint, c_void_p, c_void_p]),
+    "toyni_pow_check_host": (c_int, [c_void_p, c_size, c_u64, ctypes.c_uint, ctypes.POINTER(c_int)]),
     # section 3c
     "toyni_fri_fold_commit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

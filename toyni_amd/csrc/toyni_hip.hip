@@ -26,6 +26,7 @@
 #include "merkle_kernels.hpp"
 #include "prover_kernels.hpp"
 #include "transcript_kernels.hpp"
+#include "pow_kernels.hpp"
 
 using namespace toyni;
 
@@ -1652,6 +1653,38 @@ __global__ void __launch_bounds__(256) fri_query_positions_kernel(const uint32_t
                                                                   uint32_t* __restrict__ out) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) out[t] = fri_query_position(indices, count, m0, t);
+}
+
+// ---- a proof-of-work nonce on that transcript (pow_kernels.hpp; include/toyni_hip.h 3n) ----
+// One chain of three launches on one word of device memory: arm (one wave), search (the whole chip), finish (one wave).  The search
+// waits for nothing: a workgroup hashes the state's full blocks once on one lane (the midstate, through LDS behind the kernel's only
+// barrier), then every thread walks its candidates until pow_stop says that none of them can be the minimum any more.
+__global__ void __launch_bounds__(TRANSCRIPT_T) pow_arm_kernel(TranscriptState* __restrict__ tr, uint64_t* __restrict__ nonce) {
+    if (threadIdx.x == 0) pow_arm(*tr, nonce);
+}
+// The state's length lives in device memory, so the host cannot choose between the one-block and the two-block candidate: ONE kernel
+// holds both instantiations of the loop and takes one of them on a value that is the same in every thread of the launch -- a branch
+// around the loops, none inside them.
+template <bool TWO>
+__device__ __forceinline__ void pow_search_body(const TranscriptState& tr, uint32_t len, const Sha256State& mid, uint32_t bits, uint64_t start,
+                                                uint64_t tries, uint64_t* best) {
+    const PowTail<TWO> tail = pow_tail<TWO>(tr, len);
+    pow_search<TWO>(mid, tail, len & 63u, bits, start, tries, (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, (uint64_t)gridDim.x * blockDim.x, best);
+}
+__global__ void __launch_bounds__(POW_T) pow_search_kernel(const TranscriptState* __restrict__ tr, uint32_t bits, uint64_t start, uint64_t tries,
+                                                           uint64_t* best) {
+    __shared__ Sha256State mid;
+    if (tr->status != 0u) return;                                   // the same in every thread: nobody is left at the barrier
+    const uint32_t len = TOYNI_UNIFORM(tr->len);
+    if (threadIdx.x == 0) mid = pow_midstate(*tr, len);
+    __syncthreads();
+    const Sha256State m = mid;
+    if (pow_two_blocks(len)) pow_search_body<true>(*tr, len, m, bits, start, tries, best);
+    else pow_search_body<false>(*tr, len, m, bits, start, tries, best);
+}
+__global__ void __launch_bounds__(TRANSCRIPT_T) pow_finish_kernel(TranscriptState* __restrict__ tr, uint64_t* __restrict__ nonce, uint32_t bits,
+                                                                  uint32_t top) {
+    if (threadIdx.x == 0) pow_finish(*tr, nonce, bits, top != 0u);
 }
 
 // ---- the commit phase on that transcript (include/toyni_hip.h 3l) ----
@@ -3763,6 +3796,30 @@ int toyni_transcript_squeeze_indices_device(toyni_transcript* d_tr, size_t count
     hipLaunchKernelGGL(transcript_squeeze_indices_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, (hipStream_t)stream, transcript_of(d_tr), (uint32_t)count, max,
                        d_out);
     return (int)hipGetLastError();
+}
+
+// ---- the proof-of-work nonce (include/toyni_hip.h 3n): arm, search, finish on the word d_nonce ----
+int toyni_transcript_grind_device(toyni_transcript* d_tr, unsigned bits, uint64_t start, unsigned log_tries, uint64_t* d_nonce, void* stream) {
+    if (!d_tr || !d_nonce) return TOYNI_E_NULL;
+    if (((uintptr_t)d_tr & 15) || ((uintptr_t)d_nonce & 7)) return TOYNI_E_RANGE;
+    if (bits > TOYNI_POW_MAX_BITS || log_tries > TOYNI_POW_MAX_LOG_TRIES) return TOYNI_E_RANGE;
+    const uint64_t tries = (uint64_t)1 << log_tries;
+    if (start > ~(uint64_t)0 - (tries - 1u)) return TOYNI_E_RANGE;   // start + 2^log_tries would pass 2^64
+    const hipStream_t s = (hipStream_t)stream;
+    TranscriptState* tr = transcript_of(d_tr);
+    hipLaunchKernelGGL(pow_arm_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, s, tr, d_nonce);
+    hipLaunchKernelGGL(pow_search_kernel, dim3(pow_grid_blocks(bits, log_tries)), dim3(POW_T), 0, s, static_cast<const TranscriptState*>(tr), (uint32_t)bits,
+                       start, tries, d_nonce);
+    hipLaunchKernelGGL(pow_finish_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, s, tr, d_nonce, (uint32_t)bits,
+                       start + (tries - 1u) == ~(uint64_t)0 ? 1u : 0u);
+    return (int)hipGetLastError();
+}
+
+int toyni_pow_check_host(const uint8_t* state, size_t len, uint64_t nonce, unsigned bits, int* accepted) {
+    if (!accepted || (!state && len)) return TOYNI_E_NULL;
+    if (bits > TOYNI_POW_MAX_BITS) return TOYNI_E_RANGE;
+    *accepted = pow_check_bytes(state, (uint64_t)len, nonce, (uint32_t)bits) ? 1 : 0;
+    return TOYNI_OK;
 }
 
 int toyni_fri_query_positions_device(const uint32_t* d_indices, size_t count, size_t m0, size_t final_size, uint32_t* d_out, void* stream) {

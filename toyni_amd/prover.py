@@ -494,6 +494,30 @@ def column_scan_ext_device(ctx, num, den, out: int, out_stride: int, n: int, bat
 
 # ---- the Fiat-Shamir transcript in device memory and the commit phases on it (include/toyni_hip.h 3l) ----
 TRANSCRIPT_CAPACITY = 1008
+POW_MAX_BITS = 32
+POW_MAX_LOG_TRIES = 40
+POW_WINDOW_SLACK = 8         # default window of a grind: 2^(bits + 8) candidates -- a window without a hit has probability e^-256
+
+
+def pow_default_log_tries(bits: int) -> int:
+    """The window DeviceTranscript.grind searches when the caller names none: a search ends at its first hit, so the window only bounds
+    a search that has none -- and that one occupies the whole device until the window is exhausted (2^40 candidates are most of a
+    minute).  bits + 8 keeps a failing call at 256 times the expected work of a succeeding one."""
+    return min(POW_MAX_LOG_TRIES, bits + POW_WINDOW_SLACK)
+
+
+def pow_check(state: bytes, nonce: int, bits: int) -> bool:
+    """accept(state, nonce, bits) of include/toyni_hip.h 3n on the host (toyni_pow_check_host): what a verifier computes before it
+    absorbs the nonce's 8 little-endian bytes."""
+    state = bytes(state)
+    if not 0 <= nonce < 1 << 64:
+        raise ValueError("a proof-of-work nonce is a 64-bit value")
+    if not 0 <= bits <= POW_MAX_BITS:
+        raise ValueError(f"proof-of-work bits lie in 0..{POW_MAX_BITS}")
+    accepted = ctypes.c_int(-1)
+    buf = (ctypes.c_uint8 * len(state)).from_buffer_copy(state) if state else None
+    check(lib.toyni_pow_check_host(buf, len(state), nonce, bits, ctypes.byref(accepted)), "proof-of-work check failed")
+    return bool(accepted.value)
 
 
 class DeviceTranscript:
@@ -533,6 +557,16 @@ class DeviceTranscript:
     def squeeze_indices(self, d_out: int, count: int, mx: int, stream: int = 0) -> None:
         """`count` distinct values below `mx`, in order of first appearance, to d_out."""
         check(lib.toyni_transcript_squeeze_indices_device(self.ptr, count, mx, d_out, stream or None), "GPU transcript index squeeze failed")
+
+    def grind(self, d_nonce: int, bits: int, start: int = 0, log_tries: int = None, stream: int = 0) -> None:
+        """Proof of work (include/toyni_hip.h 3n): the smallest nonce of [start, start + 2^log_tries) whose SHA256(state || LE64(nonce))
+        has `bits` leading zero bits goes to the device word d_nonce (8-byte aligned) and its 8 bytes are absorbed.  A window without
+        one sets the status and leaves the state as it is, with *d_nonce = 0 -- after the WHOLE window has been hashed: log_tries
+        defaults to pow_default_log_tries(bits) = min(40, bits + 8); name a wider one only where the time of a failing call is
+        acceptable."""
+        if log_tries is None:
+            log_tries = pow_default_log_tries(min(max(int(bits), 0), POW_MAX_BITS))
+        check(lib.toyni_transcript_grind_device(self.ptr, bits, start, log_tries, d_nonce or None, stream or None), "GPU transcript grind failed")
 
     def download(self):
         """(state bytes, status) after a synchronous copy (the default stream: synchronise the stream that carries the work first)."""
