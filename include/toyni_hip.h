@@ -791,6 +791,64 @@ int toyni_transcript_grind_device(toyni_transcript* d_tr, unsigned bits, uint64_
 int toyni_pow_check_host(const uint8_t* state, size_t len, uint64_t nonce, unsigned bits, int* accepted);
 
 /* ------------------------------------------------------------------------------------------------
+ * 3o. From the quotient's root onward without the host: the out-of-domain point z, the out-of-domain values, the DEEP weights and the
+ *     DEEP layer of 3h with everything that depends on a challenge read from DEVICE memory.  The host-argument calls of 3h take z, the
+ *     weights and the claimed values as host arrays, which costs a caller of 3l a download and a synchronisation per step; with the
+ *     calls below the sequence
+ *         toyni_transcript_squeeze_ext_point_device -> toyni_poly_eval_ext_batch_dz_device (once per matrix, into one buffer)
+ *         -> toyni_transcript_absorb_fields_device -> toyni_transcript_squeeze_device (4 words per DEEP term)
+ *         -> toyni_deep_combine_ext_dz_device (once per matrix) -> toyni_merkle_commit_rows_device -> toyni_transcript_absorb_device
+ *         -> a commit phase of 3l or 3m -> toyni_transcript_squeeze_indices_device -> toyni_fri_query_positions_device,
+ *            toyni_query_rows_device -> the openers
+ *     only enqueues.  Conventions of 3h and 3l: asynchronous on `stream`, packed-u32 words, the sticky `status` of toyni_transcript, no
+ *     callback, no host read, no environment variable; on a warm context each call is a linear chain of kernels and can be captured
+ *     into a HIP graph (caveat of section 4; the one exception is named at toyni_deep_combine_ext_dz_device).  Host arrays (`mults`,
+ *     `slots`, `offsets`) may be reused as soon as the call returns.  Every field word read from device memory (z, a weight, a claimed
+ *     value, an absorbed word) is reduced mod p by the one-wave kernel that first touches it, as BabyBear::new does: the result is that
+ *     of the host-argument call on the reduced values.  Refusals happen on the host before anything is enqueued, the outputs untouched.
+ * ---------------------------------------------------------------------------------------------- */
+/* The protocol's out-of-domain point: four challenges (toyni_transcript_squeeze_device, count 4), squeezed again while
+ * z1 = z2 = z3 = 0 (a z in the base field could lie on the evaluation domain); d_z receives the four words of the accepted z.  One
+ * launch of one wave.  At most 8 tries: after the eighth rejection (probability p^-24) d_z is zeros, the state stays as it was and
+ * status = TOYNI_E_RANGE.  A transcript whose status is set writes zeros.  TOYNI_E_NULL for a null pointer; TOYNI_E_RANGE for a d_tr that
+ * is not 16-byte or a d_z that is not 4-byte aligned. */
+int toyni_transcript_squeeze_ext_point_device(toyni_transcript* d_tr, uint32_t* d_z, void* stream);
+/* absorb_field (src/transcript.rs) for `count` words of device memory: per word the 8 little-endian bytes of its canonical residue;
+ * byte for byte toyni_transcript_absorb_device of the expanded bytes.  count <= 126 (126 x 8 = TOYNI_TRANSCRIPT_CAPACITY), otherwise
+ * TOYNI_E_RANGE; count == 0 enqueues nothing; an overflow the host cannot see sets the status by 3l's rule.  TOYNI_E_NULL for a null
+ * d_tr, or a null d_words with count > 0. */
+int toyni_transcript_absorb_fields_device(toyni_transcript* d_tr, const uint32_t* d_words, size_t count, void* stream);
+/* toyni_poly_eval_ext_batch_device at the points mults[p] * z: z is four words of device memory, mults a host array of npoints
+ * canonical base-field multipliers (1, and the trace generator g for a column that is also opened at g z).  Three launches: a
+ * one-wave kernel expands the points into a record behind the partial sums in the context's per-stream buffer (per point 20
+ * dependent Ext squarings), then the two stages of 3h read the record.  The output bytes are those of the host-point call.  Refusals
+ * are those of the host-point call, with "a point >= p" read as "a multiplier >= p", and a null or misaligned d_z. */
+int toyni_poly_eval_ext_batch_dz_device(toyni_ntt_ctx* ctx, const uint32_t* d_coeffs, size_t ncoeffs, size_t stride, size_t batch,
+                                        const uint32_t* d_z, const uint32_t* mults, unsigned npoints, uint32_t* d_out, void* stream);
+/* Term t of toyni_deep_combine_ext_dz_device: (column, rotation) as in toyni_deep_ext_term; its weight is the Ext element
+ * d_alphas[4 alpha_index ..], its claimed value d_claims[4 value_index ..]. */
+typedef struct { uint32_t column, rotation, alpha_index, value_index; } toyni_deep_ext_slot;
+/* toyni_deep_combine_ext_device with z, the weights and the claimed values in device memory; the per-matrix calls of a proof share
+ * one array of weights and one buffer of out-of-domain values as they lie.  A one-wave kernel writes the Montgomery forms of the
+ * weights into the term table, C = sum_t alpha_t value_t and the expansion of z (the conjugates' cubic and the norm) into a record in
+ * the per-stream buffer; the combine kernel reads both.  The (column, rotation) sort does not depend on z and stays on the host.
+ * The output bytes are those of toyni_deep_combine_ext_device on the same values, the x_i = z rule, accumulate and both load widths
+ * included; nslots == 0 behaves as nterms == 0 there.  Up to 64 slots travel in the kernel arguments and the call can be captured; a
+ * longer table goes through the pinned staging ring as in 3h and cannot.  Refusals: those of toyni_deep_combine_ext_device that do not
+ * concern a host value; TOYNI_E_RANGE for an alpha_index or value_index >= 2^20 or a misaligned d_z, d_alphas or d_claims;
+ * TOYNI_E_NULL for a null d_z, d_alphas or d_claims.  Staying inside the two arrays is the caller's contract, as with the indices
+ * of 3d. */
+int toyni_deep_combine_ext_dz_device(toyni_ntt_ctx* ctx, const uint32_t* d_values, size_t width, size_t col_stride, unsigned log_blowup,
+                                     uint32_t shift, const uint32_t* d_z, const uint32_t* d_alphas, const uint32_t* d_claims,
+                                     const toyni_deep_ext_slot* slots, size_t nslots, int accumulate, uint32_t* d_out, void* stream);
+/* d_out[q * noffsets + r] = (d_indices[q] + offsets[r]) mod n, the sum in 64 bits: the rows a matrix with next-row terms opens per
+ * query -- (i, (i + B) mod N) -- in wire order, from device-resident query indices; the list feeds toyni_merkle_open_rows_device as
+ * it lies.  offsets: host array, 1 <= noffsets <= 8, every offset < n; 1 <= n <= 2^32; count <= 65536 (count == 0 enqueues nothing).
+ * Outside that: TOYNI_E_RANGE; a null pointer: TOYNI_E_NULL. */
+int toyni_query_rows_device(const uint32_t* d_indices, size_t count, size_t n, const uint32_t* offsets, unsigned noffsets,
+                            uint32_t* d_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:
  *     src/fibonacci.rs:133-150,186-198,222-245, src/math/polynomial.rs:134-144, src/merkle.rs:50-80).  All asynchronous on
  *     `stream`; packed u32 device data; ctx = a context of size N = the LDE size (its domain table supplies x_i = shift w_N^i).

@@ -160,6 +160,13 @@ SIGNATURES = {
     # section 3n
     "toyni_transcript_grind_device": (c_int, [c_void_p, ctypes.c_uint, c_u64, ctypes.c_uint, c_void_p, c_void_p]),
     "toyni_pow_check_host": (c_int, [c_void_p, c_size, c_u64, ctypes.c_uint, ctypes.POINTER(c_int)]),
+    # section 3o
+    "toyni_transcript_squeeze_ext_point_device": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "toyni_transcript_absorb_fields_device": (c_int, [c_void_p, c_void_p, c_size, c_void_p]),
+    "toyni_poly_eval_ext_batch_dz_device": (c_int, [c_void_p, c_void_p, c_size, c_size, c_size, c_void_p, c_void_p, ctypes.c_uint, c_void_p, c_void_p]),
+    "toyni_deep_combine_ext_dz_device": (c_int, [c_void_p, c_void_p, c_size, c_size, ctypes.c_uint, c_u32, c_void_p, c_void_p, c_void_p, c_void_p, c_size,
+                                                 c_int, c_void_p, c_void_p]),
+    "toyni_query_rows_device": (c_int, [c_void_p, c_size, c_size, c_void_p, ctypes.c_uint, c_void_p, c_void_p]),
     # section 3c
     "toyni_fri_fold_commit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -1143,13 +1143,16 @@ struct PolyExtArgs {
     uint32_t* out;                               // [column][point][4]
     PolyExtPowers thread[POLY_MAX_POINTS], chunk[POLY_MAX_POINTS];
 };
-TOYNI_HD void poly_ext_load(const PolyExtArgs& a, uint32_t col, uint32_t chunk, uint32_t t, uint32_t (&c)[POLY_PER_THREAD]) {
+// (the shape fields are read through a template: the device-record twins of 3o carry them in a PolyExtDzArgs, dz_kernels.hpp)
+template <class Args>
+TOYNI_HD void poly_ext_load(const Args& a, uint32_t col, uint32_t chunk, uint32_t t, uint32_t (&c)[POLY_PER_THREAD]) {
     const uint32_t* src = a.coeffs + (uint64_t)col * a.stride;
     const uint64_t base = (uint64_t)chunk * POLY_CHUNK + (uint64_t)t * POLY_PER_THREAD;
 #pragma unroll
     for (uint32_t j = 0; j < POLY_PER_THREAD; ++j) c[j] = base + j < a.ncoeffs ? src[base + j] : 0u;
 }
-TOYNI_HD uint64_t poly_ext_partial_index(const PolyExtArgs& a, uint32_t col, uint32_t chunk, uint32_t p) {
+template <class Args>
+TOYNI_HD uint64_t poly_ext_partial_index(const Args& a, uint32_t col, uint32_t chunk, uint32_t p) {
     return (((uint64_t)col * a.nblocks + chunk) * a.npoints + p) * 4u;
 }
 // r * base^e for e < POLY_THREADS, base^(2^i) = pw.sq[i]
@@ -1160,8 +1163,7 @@ TOYNI_HD Ext4 poly_ext_times_power(const PolyExtPowers& pw, Ext4 r, uint32_t e) 
     return r;
 }
 // the 16 coefficients of one thread: sum_j c_j z^j by Horner (the coefficient enters coordinate 0), then times z^(16 t)
-TOYNI_HD Ext4 poly_ext_thread_term(const PolyExtArgs& a, uint32_t p, const uint32_t (&c)[POLY_PER_THREAD], uint32_t t) {
-    const PolyExtPowers& pw = a.thread[p];
+TOYNI_HD Ext4 poly_ext_thread_term(const PolyExtPowers& pw, const uint32_t (&c)[POLY_PER_THREAD], uint32_t t) {
     Ext4 r = {{c[POLY_PER_THREAD - 1], 0u, 0u, 0u}};
 #pragma unroll
     for (int j = (int)POLY_PER_THREAD - 2; j >= 0; --j) {
@@ -1170,10 +1172,13 @@ TOYNI_HD Ext4 poly_ext_thread_term(const PolyExtArgs& a, uint32_t p, const uint3
     }
     return poly_ext_times_power(pw, r, t);
 }
+TOYNI_HD Ext4 poly_ext_thread_term(const PolyExtArgs& a, uint32_t p, const uint32_t (&c)[POLY_PER_THREAD], uint32_t t) {
+    return poly_ext_thread_term(a.thread[p], c, t);
+}
 // stage 2, thread t of POLY_THREADS: its share of sum_chunk partial[col][chunk][p] * (z^POLY_CHUNK)^chunk -- the chunks t, t + 256, ...
 // by Horner in (z^POLY_CHUNK)^256 from the last one down, then times (z^POLY_CHUNK)^t
-TOYNI_HD Ext4 poly_ext_final_thread(const PolyExtArgs& a, uint32_t col, uint32_t p, uint32_t t) {
-    const PolyExtPowers& pw = a.chunk[p];
+template <class Args>
+TOYNI_HD Ext4 poly_ext_final_thread(const Args& a, const PolyExtPowers& pw, uint32_t col, uint32_t p, uint32_t t) {
     Ext4 r = {{0u, 0u, 0u, 0u}};
     if (t >= a.nblocks) return r;
     for (uint32_t k = (a.nblocks - 1u - t) / POLY_THREADS + 1u; k-- > 0u;) {
@@ -1183,6 +1188,9 @@ TOYNI_HD Ext4 poly_ext_final_thread(const PolyExtArgs& a, uint32_t col, uint32_t
         for (int q = 0; q < 4; ++q) r.c[q] = bb_add(r.c[q], w[q]);
     }
     return poly_ext_times_power(pw, r, t);
+}
+TOYNI_HD Ext4 poly_ext_final_thread(const PolyExtArgs& a, uint32_t col, uint32_t p, uint32_t t) {
+    return poly_ext_final_thread(a, a.chunk[p], col, p, t);
 }
 
 // ---- one output of an Ext FRI round that commits what it folds (include/toyni_hip.h 3j) ----

@@ -27,6 +27,7 @@
 #include "prover_kernels.hpp"
 #include "transcript_kernels.hpp"
 #include "pow_kernels.hpp"
+#include "dz_kernels.hpp"
 
 using namespace toyni;
 
@@ -1653,6 +1654,77 @@ __global__ void __launch_bounds__(256) fri_query_positions_kernel(const uint32_t
                                                                   uint32_t* __restrict__ out) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) out[t] = fri_query_position(indices, count, m0, t);
+}
+
+// ---- from the quotient root onward without the host (dz_kernels.hpp; include/toyni_hip.h 3o) ----
+// The preparation kernels are ONE wave each: what they compute is a handful of dependent Ext products per point (or per term), far
+// below what a launch costs, and a wave needs no barrier.  The hot kernels are the bodies of 3h with the z-dependent constants read
+// from the record those kernels leave in the stream's buffer instead of from the kernel arguments.
+__global__ void __launch_bounds__(TRANSCRIPT_T) transcript_squeeze_ext_point_kernel(TranscriptState* __restrict__ tr, uint32_t* __restrict__ z) {
+    if (threadIdx.x == 0) transcript_squeeze_ext_point(*tr, z);
+}
+__global__ void __launch_bounds__(TRANSCRIPT_T) transcript_absorb_fields_kernel(TranscriptState* __restrict__ tr, const uint32_t* __restrict__ words,
+                                                                                 uint32_t count) {
+    transcript_absorb_fields_wave(*tr, words, count, threadIdx.x, TRANSCRIPT_T);
+}
+__global__ void __launch_bounds__(256) query_rows_kernel(const uint32_t* __restrict__ indices, const QueryRowOffsets off, uint32_t noffsets, uint64_t n,
+                                                         uint64_t total, uint32_t* __restrict__ out) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) out[t] = query_row(indices, off, noffsets, n, t);
+}
+// lane p: the two tables of point mults[p] * z
+__global__ void __launch_bounds__(TRANSCRIPT_T) poly_ext_prepare_kernel(const uint32_t* __restrict__ z, const PolyDzMults mults, uint32_t npoints,
+                                                                        PolyExtRecord* __restrict__ rec) {
+    if (threadIdx.x < npoints) poly_ext_record_point(z, mults.v[threadIdx.x], rec->thread[threadIdx.x], rec->chunk[threadIdx.x]);
+}
+__global__ void __launch_bounds__(256) poly_eval_ext_batch_partial_dz_kernel(const PolyExtDzArgs a, const PolyExtRecord* __restrict__ rec) {
+    __shared__ uint32_t red[256];
+    for (uint32_t col = blockIdx.y; col < a.batch; col += gridDim.y) {
+        uint32_t c[POLY_PER_THREAD];
+        poly_ext_load(a, col, blockIdx.x, threadIdx.x, c);
+        for (uint32_t p = 0; p < a.npoints; ++p) {
+            const Ext4 v = poly_ext_thread_term(rec->thread[p], c, threadIdx.x);
+            uint32_t* dst = a.partial + poly_ext_partial_index(a, col, blockIdx.x, p);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t sum = block_sum_mod(v.c[k], red);
+                if (threadIdx.x == 0) dst[k] = sum;
+            }
+        }
+    }
+}
+__global__ void __launch_bounds__(256) poly_eval_ext_batch_final_dz_kernel(const PolyExtDzArgs a, const PolyExtRecord* __restrict__ rec) {
+    __shared__ uint32_t red[256];
+    for (uint32_t col = blockIdx.x; col < a.batch; col += gridDim.x)
+        for (uint32_t p = 0; p < a.npoints; ++p) {
+            const Ext4 v = poly_ext_final_thread(a, rec->chunk[p], col, p, threadIdx.x);
+            uint32_t* dst = a.out + ((uint64_t)col * a.npoints + p) * 4u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t sum = block_sum_mod(v.c[k], red);
+                if (threadIdx.x == 0) dst[k] = sum;
+            }
+        }
+}
+// the slots inside the kernel arguments (capturable) ...
+__global__ void __launch_bounds__(TRANSCRIPT_T) deep_ext_prepare_inline_kernel(const DeepExtInlineSlots in, uint32_t nslots, const uint32_t* __restrict__ z,
+                                                                               const uint32_t* __restrict__ alphas, const uint32_t* __restrict__ claims,
+                                                                               DeepExtRecord* __restrict__ rec) {
+    __shared__ uint32_t part[4 * TRANSCRIPT_T];
+    deep_ext_prepare(in.s, nslots, z, alphas, claims, rec, part, threadIdx.x, TRANSCRIPT_T);
+}
+// ... or in device memory (any length)
+__global__ void __launch_bounds__(TRANSCRIPT_T) deep_ext_prepare_kernel(const DeepExtSlot* __restrict__ slots, uint32_t nslots, const uint32_t* __restrict__ z,
+                                                                        const uint32_t* __restrict__ alphas, const uint32_t* __restrict__ claims,
+                                                                        DeepExtRecord* __restrict__ rec) {
+    __shared__ uint32_t part[4 * TRANSCRIPT_T];
+    deep_ext_prepare(slots, nslots, z, alphas, claims, rec, part, threadIdx.x, TRANSCRIPT_T);
+}
+// deep_combine_ext_kernel with C, adj_z, m_z and the table from the record
+__global__ void __launch_bounds__(256) deep_combine_ext_dz_kernel(const DeepExtArgs a, const DeepExtRecord* __restrict__ rec) {
+    DeepExtArgs b = a;
+    deep_ext_args_from_record(b, *rec);
+    deep_combine_ext_body(b, deep_ext_record_table(rec));
 }
 
 // ---- a proof-of-work nonce on that transcript (pow_kernels.hpp; include/toyni_hip.h 3n) ----
@@ -4385,6 +4457,133 @@ int toyni_deep_combine_ext_device(toyni_ntt_ctx* c, const uint32_t* d_values, si
     std::memcpy(h, table.data(), nterms * sizeof(DeepExtTerm));
     HIPCHK(hipMemcpyAsync(sc.d_lde32, h, nterms * sizeof(DeepExtTerm), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(deep_combine_ext_kernel, grid, dim3(256), 0, s, a, reinterpret_cast<const DeepExtTerm*>(sc.d_lde32));
+    return (int)hipGetLastError();
+}
+
+// ---- section 3o: the same two steps with z, the weights and the claimed values in device memory, and the helpers around them ----
+int toyni_transcript_squeeze_ext_point_device(toyni_transcript* d_tr, uint32_t* d_z, void* stream) {
+    if (!d_tr || !d_z) return TOYNI_E_NULL;
+    if (((uintptr_t)d_tr & 15) || ((uintptr_t)d_z & 3)) return TOYNI_E_RANGE;
+    hipLaunchKernelGGL(transcript_squeeze_ext_point_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, (hipStream_t)stream, transcript_of(d_tr), d_z);
+    return (int)hipGetLastError();
+}
+
+int toyni_transcript_absorb_fields_device(toyni_transcript* d_tr, const uint32_t* d_words, size_t count, void* stream) {
+    if (!d_tr || (!d_words && count)) return TOYNI_E_NULL;
+    if (((uintptr_t)d_tr & 15) || ((uintptr_t)d_words & 3) || count > TRANSCRIPT_MAX_FIELDS) return TOYNI_E_RANGE;
+    if (count == 0) return TOYNI_OK;
+    hipLaunchKernelGGL(transcript_absorb_fields_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, (hipStream_t)stream, transcript_of(d_tr), d_words, (uint32_t)count);
+    return (int)hipGetLastError();
+}
+
+int toyni_query_rows_device(const uint32_t* d_indices, size_t count, size_t n, const uint32_t* offsets, unsigned noffsets, uint32_t* d_out, void* stream) {
+    if (!d_indices || !d_out || !offsets) return TOYNI_E_NULL;
+    if (((uintptr_t)d_indices & 3) || ((uintptr_t)d_out & 3) || noffsets < 1 || noffsets > QUERY_ROWS_MAX_OFFSETS || n < 1 ||
+        (uint64_t)n > ((uint64_t)1 << 32) || count > 65536)
+        return TOYNI_E_RANGE;
+    QueryRowOffsets off{};
+    for (unsigned r = 0; r < noffsets; ++r) {
+        if (offsets[r] >= n) return TOYNI_E_RANGE;
+        off.v[r] = offsets[r];
+    }
+    if (count == 0) return TOYNI_OK;
+    const uint64_t total = (uint64_t)count * noffsets;
+    hipLaunchKernelGGL(query_rows_kernel, dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, d_indices, off, (uint32_t)noffsets, (uint64_t)n, total,
+                       d_out);
+    return (int)hipGetLastError();
+}
+
+int toyni_poly_eval_ext_batch_dz_device(toyni_ntt_ctx* c, const uint32_t* d_coeffs, size_t ncoeffs, size_t stride, size_t batch, const uint32_t* d_z,
+                                        const uint32_t* mults, unsigned npoints, uint32_t* d_out, void* stream) {
+    if (!c || !d_z || !mults || !d_out || (!d_coeffs && ncoeffs)) return TOYNI_E_NULL;
+    if (npoints < 1 || npoints > (unsigned)POLY_MAX_POINTS) return TOYNI_E_RANGE;
+    PolyDzMults m{};
+    for (unsigned p = 0; p < npoints; ++p) {
+        if (mults[p] >= BB_P) return TOYNI_E_RANGE;
+        m.v[p] = mults[p];
+    }
+    if ((batch > 1 && stride < ncoeffs) || batch > 0xFFFFFFFFull || (((uintptr_t)d_coeffs | (uintptr_t)d_out | (uintptr_t)d_z) & 3)) return TOYNI_E_RANGE;
+    if (batch == 0) return TOYNI_OK;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (ncoeffs == 0) return (int)hipMemsetAsync(d_out, 0, batch * npoints * 4 * sizeof(uint32_t), s);   // zero polynomials
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    PolyExtDzArgs a{};
+    a.coeffs = d_coeffs;
+    a.ncoeffs = ncoeffs;
+    a.stride = stride;
+    a.batch = (uint32_t)batch;
+    a.npoints = npoints;
+    a.nblocks = (uint32_t)((ncoeffs + POLY_CHUNK - 1) / POLY_CHUNK);
+    // the stream's buffer: the partial sums (a multiple of four words), then the record
+    const size_t partial_words = batch * a.nblocks * npoints * 4;
+    int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words, partial_words + sizeof(PolyExtRecord) / sizeof(uint32_t), sizeof(uint32_t));
+    if (rc) return rc;
+    a.partial = sc.d_lde32;
+    a.out = d_out;
+    PolyExtRecord* rec = reinterpret_cast<PolyExtRecord*>(sc.d_lde32 + partial_words);
+    hipLaunchKernelGGL(poly_ext_prepare_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, s, d_z, m, (uint32_t)npoints, rec);
+    const unsigned rows = (unsigned)std::min<size_t>(batch, 65535);
+    hipLaunchKernelGGL(poly_eval_ext_batch_partial_dz_kernel, dim3(a.nblocks, rows), dim3(POLY_THREADS), 0, s, a,
+                       static_cast<const PolyExtRecord*>(rec));
+    hipLaunchKernelGGL(poly_eval_ext_batch_final_dz_kernel, dim3(rows), dim3(POLY_THREADS), 0, s, a, static_cast<const PolyExtRecord*>(rec));
+    return (int)hipGetLastError();
+}
+
+int toyni_deep_combine_ext_dz_device(toyni_ntt_ctx* c, const uint32_t* d_values, size_t width, size_t col_stride, unsigned log_blowup, uint32_t shift,
+                                     const uint32_t* d_z, const uint32_t* d_alphas, const uint32_t* d_claims, const toyni_deep_ext_slot* slots,
+                                     size_t nslots, int accumulate, uint32_t* d_out, void* stream) {
+    if (!c || !d_values || !d_out || !d_z || !d_alphas || !d_claims || (!slots && nslots)) return TOYNI_E_NULL;
+    const int log_N = c->plan.log_n;
+    const uint64_t N = 1ull << log_N;
+    if ((int)log_blowup > log_N || shift == 0 || shift >= BB_P || width == 0 || width > 65536 || col_stride < N || nslots > ((size_t)1 << 20) ||
+        (((uintptr_t)d_values | (uintptr_t)d_z | (uintptr_t)d_alphas | (uintptr_t)d_claims) & 3) || ((uintptr_t)d_out & 15))
+        return TOYNI_E_RANGE;
+    for (size_t t = 0; t < nslots; ++t)
+        if (slots[t].column >= width || slots[t].rotation >= (N >> log_blowup) || slots[t].alpha_index >= (1u << 20) || slots[t].value_index >= (1u << 20))
+            return TOYNI_E_RANGE;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (nslots == 0) return accumulate ? TOYNI_OK : (int)hipMemsetAsync(d_out, 0, N * 4 * sizeof(uint32_t), s);
+    // the slots in the order of the table the kernel reads: sorted by (column, rotation), which does not depend on z
+    std::vector<DeepExtSlot> sorted(nslots);
+    for (size_t t = 0; t < nslots; ++t)
+        sorted[t] = DeepExtSlot{slots[t].column, (uint32_t)((uint64_t)slots[t].rotation << log_blowup), slots[t].alpha_index, slots[t].value_index};
+    std::stable_sort(sorted.begin(), sorted.end(), [](const DeepExtSlot& x, const DeepExtSlot& y) { return x.column != y.column ? x.column < y.column : x.rot < y.rot; });
+    DeepExtArgs a{};
+    a.values = d_values;
+    a.out = d_out;
+    a.col_stride = col_stride;
+    a.dom = domain_args(c, (unsigned)log_N, shift);
+    a.log_N = (uint32_t)log_N;
+    a.nterms = (uint32_t)nslots;
+    a.wNR = to_mont_host(bb_root_of_unity_host((uint32_t)log_N));
+    a.accumulate = accumulate ? 1u : 0u;
+    // the stream's buffer: the record, the table the preparation kernel fills, and (a long table only) the slots it reads
+    const bool inline_slots = nslots <= DEEP_EXT_INLINE_SLOTS;
+    const size_t table_words = (sizeof(DeepExtRecord) + nslots * sizeof(DeepExtTerm)) / sizeof(uint32_t);
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words, table_words + (inline_slots ? 0 : nslots * (sizeof(DeepExtSlot) / sizeof(uint32_t))),
+                  sizeof(uint32_t));
+    if (rc) return rc;
+    DeepExtRecord* rec = reinterpret_cast<DeepExtRecord*>(sc.d_lde32);
+    if (inline_slots) {   // capturable: nothing but two launches
+        DeepExtInlineSlots in{};
+        std::copy(sorted.begin(), sorted.end(), in.s);
+        hipLaunchKernelGGL(deep_ext_prepare_inline_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, s, in, (uint32_t)nslots, d_z, d_alphas, d_claims, rec);
+    } else {              // pinned staging ring -> the stream's buffer by a stream-ordered copy, as toyni_deep_combine_ext_device
+        DeepExtSlot* d_slots = reinterpret_cast<DeepExtSlot*>(sc.d_lde32 + table_words);
+        void* h = nullptr;
+        if ((rc = ring_slice(sc, s, nslots * sizeof(DeepExtSlot), &h))) return rc;
+        std::memcpy(h, sorted.data(), nslots * sizeof(DeepExtSlot));
+        HIPCHK(hipMemcpyAsync(d_slots, h, nslots * sizeof(DeepExtSlot), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(deep_ext_prepare_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, s, static_cast<const DeepExtSlot*>(d_slots), (uint32_t)nslots, d_z,
+                           d_alphas, d_claims, rec);
+    }
+    const uint64_t items = log_N >= 2 ? N / 4 : N;
+    hipLaunchKernelGGL(deep_combine_ext_dz_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, a, static_cast<const DeepExtRecord*>(rec));
     return (int)hipGetLastError();
 }
 

@@ -158,6 +158,42 @@ def deep_combine_ext_device(ctx, d_values: int, width: int, col_stride: int, log
           "GPU Ext DEEP combination failed")
 
 
+# ---- the same two steps with z, the weights and the claimed values in device memory (include/toyni_hip.h 3o) ----
+def poly_eval_ext_batch_dz_device(ctx, d_coeffs: int, ncoeffs: int, stride: int, batch: int, d_z: int, mults, d_out: int, stream: int = 0) -> None:
+    """poly_eval_ext_batch_device at the points mults[p] * z, z four words at the device pointer d_z; mults: canonical base-field
+    multipliers (1, and g for a column that is also opened at g z)."""
+    m = np.ascontiguousarray(mults, dtype=np.uint32).ravel()
+    check(lib.toyni_poly_eval_ext_batch_dz_device(ctx.handle, d_coeffs or None, ncoeffs, stride, batch, d_z or None, m.ctypes.data, m.size, d_out,
+                                                  stream or None), "GPU batched Ext polynomial evaluation (device point) failed")
+
+
+class DeepExtSlot(ctypes.Structure):   # toyni_deep_ext_slot (include/toyni_hip.h 3o)
+    _fields_ = [("column", ctypes.c_uint32), ("rotation", ctypes.c_uint32), ("alpha_index", ctypes.c_uint32), ("value_index", ctypes.c_uint32)]
+
+
+def deep_ext_slots(columns, rotations, alpha_indices, value_indices):
+    """The slot table of deep_combine_ext_dz_device: term t weighs column columns[t], read rotations[t] trace rows ahead, by the Ext
+    element alpha_indices[t] of the device array of weights against the Ext element value_indices[t] of the device array of values."""
+    cols, rots, ais, vis = (np.asarray(v, dtype=np.uint32).ravel() for v in (columns, rotations, alpha_indices, value_indices))
+    assert cols.size == rots.size == ais.size == vis.size
+    return (DeepExtSlot * cols.size)(*[DeepExtSlot(int(c), int(r), int(a), int(v)) for c, r, a, v in zip(cols, rots, ais, vis)])
+
+
+def deep_combine_ext_dz_device(ctx, d_values: int, width: int, col_stride: int, log_blowup: int, shift: int, d_z: int, d_alphas: int, d_claims: int,
+                               slots, d_out: int, accumulate: bool = False, stream: int = 0) -> None:
+    """deep_combine_ext_device with z (d_z, four words), the weights (d_alphas) and the claimed values (d_claims) in device memory;
+    slots: what deep_ext_slots returns; d_out: 16-byte aligned."""
+    check(lib.toyni_deep_combine_ext_dz_device(ctx.handle, d_values, width, col_stride, log_blowup, shift, d_z or None, d_alphas or None,
+                                               d_claims or None, slots if len(slots) else None, len(slots), 1 if accumulate else 0, d_out,
+                                               stream or None), "GPU Ext DEEP combination (device point) failed")
+
+
+def query_rows_device(d_indices: int, count: int, n: int, offsets, d_out: int, stream: int = 0) -> None:
+    """d_out[q * len(offsets) + r] = (d_indices[q] + offsets[r]) mod n: the rows a matrix with next-row terms opens per query."""
+    off = np.ascontiguousarray(offsets, dtype=np.uint32).ravel()
+    check(lib.toyni_query_rows_device(d_indices or None, count, n, off.ctypes.data, off.size, d_out or None, stream or None), "GPU query rows failed")
+
+
 # ---- constraint programs (include/toyni_hip.h 3f) ----
 AIR_CELL, AIR_CONST, AIR_X, AIR_XINV, AIR_ADD, AIR_SUB, AIR_MUL, AIR_EMIT = range(8)
 AIR_MAX_REGS, AIR_MAX_MATRICES = 64, 4
@@ -557,6 +593,14 @@ class DeviceTranscript:
     def squeeze_indices(self, d_out: int, count: int, mx: int, stream: int = 0) -> None:
         """`count` distinct values below `mx`, in order of first appearance, to d_out."""
         check(lib.toyni_transcript_squeeze_indices_device(self.ptr, count, mx, d_out, stream or None), "GPU transcript index squeeze failed")
+
+    def squeeze_ext_point(self, d_z: int, stream: int = 0) -> None:
+        """The out-of-domain point (include/toyni_hip.h 3o): four challenges to d_z, squeezed again while z1 = z2 = z3 = 0."""
+        check(lib.toyni_transcript_squeeze_ext_point_device(self.ptr, d_z or None, stream or None), "GPU transcript point squeeze failed")
+
+    def absorb_fields(self, d_words: int, count: int, stream: int = 0) -> None:
+        """absorb_field for `count` (<= 126) device-resident words: 8 little-endian bytes of the canonical residue each."""
+        check(lib.toyni_transcript_absorb_fields_device(self.ptr, d_words or None, count, stream or None), "GPU transcript field absorb failed")
 
     def grind(self, d_nonce: int, bits: int, start: int = 0, log_tries: int = None, stream: int = 0) -> None:
         """Proof of work (include/toyni_hip.h 3n): the smallest nonce of [start, start + 2^log_tries) whose SHA256(state || LE64(nonce))
