@@ -849,6 +849,62 @@ int toyni_query_rows_device(const uint32_t* d_indices, size_t count, size_t n, c
                             uint32_t* d_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * 3p. The first half of a staged-AIR proof without the host: gamma and the constraint weights read from DEVICE memory.  3o carries a
+ *     proof from "quotient root absorbed" onward; before that the host-argument calls take gamma as toyni_ext_operand.shift (3i), as
+ *     CONST immediates of the constraint program (3f: a program per proof, and toyni_air_program_create blocks) and the weights as a
+ *     host array (3k), which costs a caller of 3l three downloads and synchronisations.  With the calls below the sequence
+ *         toyni_transcript_absorb_device (main root) -> toyni_transcript_squeeze_device (4 words: gamma)
+ *         -> toyni_column_scan_ext_dc_device -> ... commit, absorb -> toyni_transcript_squeeze_device (the alphas)
+ *         -> toyni_air_quotient_ext_dc_device -> ... commit, absorb -> 3o
+ *     only enqueues, and the constraint program is created once per AIR.  Conventions of 3o: asynchronous on `stream`, packed-u32
+ *     words, host arrays reusable on return, refusals on the host before anything is enqueued with the outputs untouched; every field
+ *     word read from device memory is reduced mod p by the one-wave kernel that first touches it, and the bytes written are those of
+ *     the host-argument call on the reduced values.  No existing entry point, record layout or written byte changes.
+ * ---------------------------------------------------------------------------------------------- */
+/* One more instruction for constraint programs: a value that is not known when the program is created. */
+#define TOYNI_AIR_PARAM 8          /* r[dst] = params[imm], imm < TOYNI_AIR_MAX_PARAMS; a and b unused */
+#define TOYNI_AIR_MAX_PARAMS 256
+/* toyni_air_program_check / _create with TOYNI_AIR_PARAM accepted (it writes dst as CONST does; TOYNI_E_RANGE for imm >= 256); every
+ * other rule is theirs.  toyni_air_info stays as it is: *nparams = highest parameter index + 1, or 0.  The calls of 3f keep refusing
+ * op 8.  A program created here WITHOUT a PARAM is accepted by every quotient call; one WITH a PARAM is refused with TOYNI_E_RANGE by
+ * toyni_air_quotient_device and toyni_air_quotient_ext_device, which have no parameter array.  TOYNI_E_NULL for a null argument. */
+int toyni_air_program_check_params(const toyni_air_insn* insns, size_t ninsns, toyni_air_info* info, uint32_t* nparams);
+int toyni_air_program_create_params(toyni_ntt_ctx* ctx, const toyni_air_insn* insns, size_t ninsns, toyni_air_program** out);
+int toyni_air_program_nparams(const toyni_air_program* prog, uint32_t* nparams);   /* 0 for a program of toyni_air_program_create */
+/* toyni_air_quotient_ext_device (3k) with the parameters and the weights in device memory.  d_params: nparams words; d_alphas:
+ * nalphas Ext elements (4 words each); the weights follow from the alphas by weights_form: */
+#define TOYNI_AIR_WEIGHTS_EXT 0        /* W_k = the Ext element d_alphas[4 k ..],            nweights = nalphas   */
+#define TOYNI_AIR_WEIGHTS_EMIT_EXT 1   /* W_{4 k + j} = alpha_k * X^j (emit_ext constraints), nweights = 4 nalphas */
+/* Two launches, a linear chain for any nweights (no staging ring: the call can always be captured, caveat of section 4): a one-wave
+ * kernel writes a record into the context's per-stream buffer -- the parameters, reduced and in Montgomery form, then the 4 x nweights
+ * plain canonical weight words (alpha * X = (11 a3, a0, a1, a2)); its lanes stride over the parameters and the alphas.  A twin of 3k's
+ * kernel takes the record as a read-only argument and fetches its words by scalar loads where they are used: PARAM is one such load.
+ * By definition the output is byte for byte what toyni_air_quotient_ext_device writes for the program with every PARAM j replaced by
+ * CONST (params[j] mod p) under the weights of the reduced alphas -- accumulate, a null d_c_out, both store widths, every launch shape
+ * and every source of 1 / Z_H of 3f included.
+ * Refused: what 3k refuses that does not concern a host value; TOYNI_E_NULL for a null d_alphas, or a null d_params with nparams > 0;
+ * TOYNI_E_RANGE for nparams < the program's nparams or > TOYNI_AIR_MAX_PARAMS, nweights < nconstraints or > 65536, an unknown form, a
+ * d_params or d_alphas that is not 4-byte aligned. */
+int toyni_air_quotient_ext_dc_device(toyni_ntt_ctx* ctx, const toyni_air_program* prog, const toyni_air_matrix* mats, size_t nmats,
+                                     unsigned log_blowup, uint32_t shift, const uint32_t* d_params, size_t nparams,
+                                     const uint32_t* d_alphas, size_t nalphas, int weights_form,
+                                     uint32_t* d_c_out, uint32_t* d_q_out, size_t out_stride, int accumulate, void* stream);
+/* toyni_column_scan_ext_device (3i) with the operands' shifts in device memory: an operand's shift is the Ext element
+ * d_challenges[4 * shift_index ..], reduced; TOYNI_EXT_SHIFT_NONE means 0; shift_index < 2^20 otherwise (staying inside the array is
+ * the caller's contract).  init stays a host array: a protocol constant, not a challenge.  A one-wave kernel writes
+ * {num shift, den shift, adj_z / m_z of z = -(den shift)} into the per-stream buffer behind the tile words of the same call, 16-byte
+ * aligned; twins of the two 3i kernels that read an operand take that record, the prefix kernel is launched as it is; with batch > 16
+ * the one record serves every launch sequence.  Launch structure, exactness, the in-place rule, load widths and the d_totals layout are
+ * those of 3i, and the output is byte for byte toyni_column_scan_ext_device with the reduced shifts.
+ * Refused: what 3i refuses, without "a shift coordinate >= p"; TOYNI_E_NULL for a null d_challenges when some operand names an index;
+ * TOYNI_E_RANGE for a d_challenges that is not 4-byte aligned or an index >= 2^20. */
+#define TOYNI_EXT_SHIFT_NONE 0xffffffffu
+typedef struct { const uint32_t* d_values; size_t stride; uint32_t width; uint32_t shift_index; } toyni_ext_operand_dc;
+int toyni_column_scan_ext_dc_device(toyni_ntt_ctx* ctx, const toyni_ext_operand_dc* num, const toyni_ext_operand_dc* den,
+                                    const uint32_t* d_challenges, uint32_t* d_out, size_t out_stride, size_t n, size_t batch, int op,
+                                    const uint32_t* init, uint32_t* d_totals, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:
  *     src/fibonacci.rs:133-150,186-198,222-245, src/math/polynomial.rs:134-144, src/merkle.rs:50-80).  All asynchronous on
  *     `stream`; packed u32 device data; ctx = a context of size N = the LDE size (its domain table supplies x_i = shift w_N^i).

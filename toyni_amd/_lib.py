@@ -167,6 +167,14 @@ SIGNATURES = {
     "toyni_deep_combine_ext_dz_device": (c_int, [c_void_p, c_void_p, c_size, c_size, ctypes.c_uint, c_u32, c_void_p, c_void_p, c_void_p, c_void_p, c_size,
                                                  c_int, c_void_p, c_void_p]),
     "toyni_query_rows_device": (c_int, [c_void_p, c_size, c_size, c_void_p, ctypes.c_uint, c_void_p, c_void_p]),
+    # section 3p
+    "toyni_air_program_check_params": (c_int, [c_void_p, c_size, c_void_p, c_void_p]),
+    "toyni_air_program_create_params": (c_int, [c_void_p, c_void_p, c_size, ctypes.POINTER(c_void_p)]),
+    "toyni_air_program_nparams": (c_int, [c_void_p, c_void_p]),
+    "toyni_air_quotient_ext_dc_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, ctypes.c_uint, c_u32, c_void_p, c_size, c_void_p, c_size, c_int,
+                                                 c_void_p, c_void_p, c_size, c_int, c_void_p]),
+    "toyni_column_scan_ext_dc_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_size, c_size, c_int, c_void_p, c_void_p,
+                                                c_void_p]),
     # section 3c
     "toyni_fri_fold_commit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -28,6 +28,7 @@
 #include "transcript_kernels.hpp"
 #include "pow_kernels.hpp"
 #include "dz_kernels.hpp"
+#include "dc_kernels.hpp"
 
 using namespace toyni;
 
@@ -1097,9 +1098,7 @@ __device__ __forceinline__ Ext4 ext_accum_block_exclusive(const Ext4& v, Ext4* w
 static_assert(EXT_ACCUM_THREADS == SCAN_THREADS, "the zero counts go through scan_block_exclusive<SCAN_COUNT>");
 // step 1, grid (tile, column): one aggregate and one zero count per tile
 template <int OP>
-__global__ void __launch_bounds__(EXT_ACCUM_THREADS) ext_accum_aggregate_kernel(const ExtAccumArgs a) {
-    __shared__ Ext4 wave_tot[EXT_ACCUM_THREADS / SCAN_WAVE];
-    __shared__ uint32_t wave_zeros[EXT_ACCUM_THREADS / SCAN_WAVE];
+__device__ __forceinline__ void ext_accum_aggregate_body(const ExtAccumArgs& a, Ext4* wave_tot, uint32_t* wave_zeros) {
     const uint32_t col = blockIdx.y, tile = blockIdx.x;
     const uint64_t i0 = (uint64_t)tile * EXT_ACCUM_TILE + (uint64_t)threadIdx.x * EXT_ACCUM_GROUP;
     Ext4 t[EXT_ACCUM_GROUP], ex[EXT_ACCUM_GROUP], total;
@@ -1113,6 +1112,12 @@ __global__ void __launch_bounds__(EXT_ACCUM_THREADS) ext_accum_aggregate_kernel(
         for (int k = 0; k < 4; ++k) agg[(uint64_t)k * a.ntiles + tile] = total.c[k];
         ext_accum_tile_zeros(a, col)[tile] = ztotal;
     }
+}
+template <int OP>
+__global__ void __launch_bounds__(EXT_ACCUM_THREADS) ext_accum_aggregate_kernel(const ExtAccumArgs a) {
+    __shared__ Ext4 wave_tot[EXT_ACCUM_THREADS / SCAN_WAVE];
+    __shared__ uint32_t wave_zeros[EXT_ACCUM_THREADS / SCAN_WAVE];
+    ext_accum_aggregate_body<OP>(a, wave_tot, wave_zeros);
 }
 // step 2, one workgroup per column: the exclusive scan of the column's aggregates, seeded with init, in rounds of EXT_ACCUM_TILE; the totals
 template <int OP>
@@ -1153,9 +1158,7 @@ __global__ void __launch_bounds__(EXT_ACCUM_THREADS) ext_accum_prefix_kernel(con
 // columns alone (n <= one tile): the prefix is init and the totals are written here.  In place on a width-4 operand: a thread has read
 // all it needs of its own elements before it stores them, and no thread reads another's.
 template <int OP>
-__global__ void __launch_bounds__(EXT_ACCUM_THREADS) ext_accum_apply_kernel(const ExtAccumArgs a, const ExtAccumSeeds in) {
-    __shared__ Ext4 wave_tot[EXT_ACCUM_THREADS / SCAN_WAVE];
-    __shared__ uint32_t wave_zeros[EXT_ACCUM_THREADS / SCAN_WAVE];
+__device__ __forceinline__ void ext_accum_apply_body(const ExtAccumArgs& a, const ExtAccumSeeds& in, Ext4* wave_tot, uint32_t* wave_zeros) {
     const uint32_t col = blockIdx.y, tile = blockIdx.x;
     const uint64_t i0 = (uint64_t)tile * EXT_ACCUM_TILE + (uint64_t)threadIdx.x * EXT_ACCUM_GROUP;
     Ext4 t[EXT_ACCUM_GROUP], ex[EXT_ACCUM_GROUP], total, seed;
@@ -1178,6 +1181,12 @@ __global__ void __launch_bounds__(EXT_ACCUM_THREADS) ext_accum_apply_kernel(cons
             for (int k = 5; k < 8; ++k) a.totals[8 * col + k] = 0u;
         }
     }
+}
+template <int OP>
+__global__ void __launch_bounds__(EXT_ACCUM_THREADS) ext_accum_apply_kernel(const ExtAccumArgs a, const ExtAccumSeeds in) {
+    __shared__ Ext4 wave_tot[EXT_ACCUM_THREADS / SCAN_WAVE];
+    __shared__ uint32_t wave_zeros[EXT_ACCUM_THREADS / SCAN_WAVE];
+    ext_accum_apply_body<OP>(a, in, wave_tot, wave_zeros);
 }
 // out[i] = in[i]^-1 (0 for 0) on one Ext column: the tower inversion alone.  zero_count (may be null) was cleared ahead of the launch.
 __global__ void __launch_bounds__(EXT_ACCUM_THREADS) ext_invert_columns_kernel(const uint32_t* in, uint64_t in_stride, uint32_t* out,
@@ -1725,6 +1734,75 @@ __global__ void __launch_bounds__(256) deep_combine_ext_dz_kernel(const DeepExtA
     DeepExtArgs b = a;
     deep_ext_args_from_record(b, *rec);
     deep_combine_ext_body(b, deep_ext_record_table(rec));
+}
+
+// ---- gamma and the constraint weights without the host (dc_kernels.hpp; include/toyni_hip.h 3p) ----
+// Two more one-wave preparation kernels, and the hot kernels of 3i and 3k with what depends on a challenge read from the record the
+// preparation left in the stream's buffer.  The argument-fed kernels above are not touched: each twin is a kernel of its own.
+__global__ void __launch_bounds__(TRANSCRIPT_T) air_dc_prepare_kernel(const uint32_t* __restrict__ params, uint32_t nparams,
+                                                                      const uint32_t* __restrict__ alphas, uint32_t nalphas, uint32_t form,
+                                                                      uint32_t* __restrict__ rec) {
+    air_dc_prepare(params, nparams, alphas, nalphas, form, rec, threadIdx.x, TRANSCRIPT_T);
+}
+// air_quotient_ext_kernel with the parameters and the weights from the record: rec[0 .. nparams) Montgomery forms, then the weights
+__global__ void __launch_bounds__(256) air_quotient_ext_dc_kernel(const AirArgs a, const uint64_t out_stride, const uint32_t* __restrict__ rec,
+                                                                  const uint32_t nparams) {
+    constexpr int K = 4;
+    const uint32_t* weights4 = rec + nparams;
+    const uint32_t B = 1u << a.log_blowup;
+    uint32_t* zh_lds = air_lds + a.nregs * blockDim.x * K;
+    if (a.zh_lds) {
+        for (uint32_t t = threadIdx.x; t < B; t += blockDim.x) zh_lds[t] = zh_inv_class(a.shift_nR, a.wBR, t);
+        __syncthreads();
+    }
+    const uint64_t N = (uint64_t)1 << a.log_N;
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (a.log_N >= 2) {
+        if (g >= N / K) return;
+        const uint64_t i0 = g * K;
+        uint32_t zhR[K], c[4][K], q[4][K];
+        if (a.zh_lds) {
+#pragma unroll
+            for (int j = 0; j < K; ++j) zhR[j] = zh_lds[(i0 + j) & (B - 1)];
+        } else if (a.divides) {
+            air_zh_inverses<K>(a, i0, zhR);
+        } else {
+#pragma unroll
+            for (int j = 0; j < K; ++j) zhR[j] = 0u;
+        }
+        air_eval_group_ext_dc<K>(a, rec, weights4, air_lds + threadIdx.x * K, blockDim.x * K, i0, zhR, c, q);
+        air_ext_store<K>(a.c_out, out_stride, i0, a.accumulate, c);
+        air_ext_store<K>(a.q_out, out_stride, i0, a.accumulate, q);
+    } else if (g < N) {
+        uint32_t zhR[1] = {0u}, c[4][1], q[4][1];
+        if (a.zh_lds) zhR[0] = zh_lds[g & (B - 1)];
+        else if (a.divides) air_zh_inverses<1>(a, g, zhR);
+        air_eval_group_ext_dc<1>(a, rec, weights4, air_lds + threadIdx.x, blockDim.x, g, zhR, c, q);
+        air_ext_store<1>(a.c_out, out_stride, g, a.accumulate, c);
+        air_ext_store<1>(a.q_out, out_stride, g, a.accumulate, q);
+    }
+}
+__global__ void __launch_bounds__(TRANSCRIPT_T) extcol_dc_prepare_kernel(const uint32_t* __restrict__ challenges, uint32_t num_index, uint32_t den_index,
+                                                                            uint32_t den_norm, ExtAccumRecord* __restrict__ rec) {
+    ext_accum_dc_prepare(challenges, num_index, den_index, den_norm, rec, threadIdx.x);
+}
+// steps 1 and 3 of 3i with the shifts and adj_z / m_z from the record (step 2 reads no operand and is launched as it is)
+template <int OP>
+__global__ void __launch_bounds__(EXT_ACCUM_THREADS) extcol_aggregate_dc_kernel(const ExtAccumArgs a, const ExtAccumRecord* __restrict__ rec) {
+    __shared__ Ext4 wave_tot[EXT_ACCUM_THREADS / SCAN_WAVE];
+    __shared__ uint32_t wave_zeros[EXT_ACCUM_THREADS / SCAN_WAVE];
+    ExtAccumArgs b = a;
+    ext_accum_args_from_record(b, *rec);
+    ext_accum_aggregate_body<OP>(b, wave_tot, wave_zeros);
+}
+template <int OP>
+__global__ void __launch_bounds__(EXT_ACCUM_THREADS) extcol_apply_dc_kernel(const ExtAccumArgs a, const ExtAccumSeeds in,
+                                                                               const ExtAccumRecord* __restrict__ rec) {
+    __shared__ Ext4 wave_tot[EXT_ACCUM_THREADS / SCAN_WAVE];
+    __shared__ uint32_t wave_zeros[EXT_ACCUM_THREADS / SCAN_WAVE];
+    ExtAccumArgs b = a;
+    ext_accum_args_from_record(b, *rec);
+    ext_accum_apply_body<OP>(b, in, wave_tot, wave_zeros);
 }
 
 // ---- a proof-of-work nonce on that transcript (pow_kernels.hpp; include/toyni_hip.h 3n) ----
@@ -2664,6 +2742,17 @@ void ext_accum_launch(const ExtAccumArgs& a, const ExtAccumSeeds& in, unsigned c
     hipLaunchKernelGGL(ext_accum_aggregate_kernel<OP>, dim3(a.ntiles, cols), dim3(EXT_ACCUM_THREADS), 0, s, a);
     hipLaunchKernelGGL(ext_accum_prefix_kernel<OP>, dim3(cols), dim3(EXT_ACCUM_THREADS), 0, s, a, in);
     hipLaunchKernelGGL(ext_accum_apply_kernel<OP>, dim3(a.ntiles, cols), dim3(EXT_ACCUM_THREADS), 0, s, a, in);
+}
+// the same for toyni_column_scan_ext_dc_device: the record instead of the shifts; step 2 is the kernel above
+template <int OP>
+void ext_accum_dc_launch(const ExtAccumArgs& a, const ExtAccumSeeds& in, const ExtAccumRecord* rec, unsigned cols, hipStream_t s) {
+    if (a.single) {
+        hipLaunchKernelGGL(extcol_apply_dc_kernel<OP>, dim3(1, cols), dim3(EXT_ACCUM_THREADS), 0, s, a, in, rec);
+        return;
+    }
+    hipLaunchKernelGGL(extcol_aggregate_dc_kernel<OP>, dim3(a.ntiles, cols), dim3(EXT_ACCUM_THREADS), 0, s, a, rec);
+    hipLaunchKernelGGL(ext_accum_prefix_kernel<OP>, dim3(cols), dim3(EXT_ACCUM_THREADS), 0, s, a, in);
+    hipLaunchKernelGGL(extcol_apply_dc_kernel<OP>, dim3(a.ntiles, cols), dim3(EXT_ACCUM_THREADS), 0, s, a, in, rec);
 }
 
 bool is_pow2(size_t v) { return v && !(v & (v - 1)); }
@@ -4732,19 +4821,22 @@ struct toyni_air_program {
     int device = 0;
     toyni_air_info info{};
     AirInsn* d_insns = nullptr;
+    uint32_t nparams = 0;    // highest PARAM index + 1 (3p); 0: the program runs under every quotient call
 };
 
-int toyni_air_program_check(const toyni_air_insn* insns, size_t ninsns, toyni_air_info* info) {
+// nparams: null for the instruction set of 3f (PARAM is an unknown op); otherwise PARAM is accepted and its highest index + 1 returned
+static int air_program_check_impl(const toyni_air_insn* insns, size_t ninsns, toyni_air_info* info, uint32_t* nparams) {
     if (!insns || !info) return TOYNI_E_NULL;
     if (ninsns == 0 || ninsns > AIR_MAX_INSNS) return TOYNI_E_RANGE;
     toyni_air_info r{};
     r.ninsns = (uint32_t)ninsns;
     bool written[AIR_MAX_REGS] = {};
     bool emitted = false;
+    uint32_t np = 0;
     const auto readable = [&](uint8_t reg) { return reg < AIR_MAX_REGS && written[reg]; };
     for (size_t k = 0; k < ninsns; ++k) {
         const toyni_air_insn& in = insns[k];
-        if (in.op >= AIR_OP_COUNT) return TOYNI_E_RANGE;
+        if (in.op >= AIR_OP_COUNT && !(nparams && in.op == TOYNI_AIR_PARAM)) return TOYNI_E_RANGE;
         if (in.op == TOYNI_AIR_EMIT) {
             if (!readable(in.a) || in.b > 1 || in.imm >= 65536) return TOYNI_E_RANGE;
             r.nconstraints = std::max(r.nconstraints, in.imm + 1);
@@ -4753,7 +4845,10 @@ int toyni_air_program_check(const toyni_air_insn* insns, size_t ninsns, toyni_ai
             continue;
         }
         if (in.dst >= AIR_MAX_REGS) return TOYNI_E_RANGE;
-        if (in.op >= TOYNI_AIR_ADD) {
+        if (in.op == TOYNI_AIR_PARAM) {
+            if (in.imm >= AIR_MAX_PARAMS) return TOYNI_E_RANGE;
+            np = std::max(np, in.imm + 1);
+        } else if (in.op >= TOYNI_AIR_ADD) {
             if (!readable(in.a) || !readable(in.b)) return TOYNI_E_RANGE;
         } else if (in.op == TOYNI_AIR_CELL) {
             if (in.b >= AIR_MAX_MATRICES || in.imm >= 65536) return TOYNI_E_RANGE;
@@ -4769,13 +4864,22 @@ int toyni_air_program_check(const toyni_air_insn* insns, size_t ninsns, toyni_ai
     for (uint32_t k = 0; k < AIR_MAX_REGS; ++k)
         if (written[k]) r.nregs = k + 1;   // a register that is read has been written
     *info = r;
+    if (nparams) *nparams = np;
     return TOYNI_OK;
 }
+int toyni_air_program_check(const toyni_air_insn* insns, size_t ninsns, toyni_air_info* info) {
+    return air_program_check_impl(insns, ninsns, info, nullptr);
+}
+int toyni_air_program_check_params(const toyni_air_insn* insns, size_t ninsns, toyni_air_info* info, uint32_t* nparams) {
+    if (!nparams) return TOYNI_E_NULL;
+    return air_program_check_impl(insns, ninsns, info, nparams);
+}
 
-int toyni_air_program_create(toyni_ntt_ctx* c, const toyni_air_insn* insns, size_t ninsns, toyni_air_program** out) {
+static int air_program_create_impl(toyni_ntt_ctx* c, const toyni_air_insn* insns, size_t ninsns, toyni_air_program** out, bool with_params) {
     if (!c || !insns || !out) return TOYNI_E_NULL;
     toyni_air_info info{};
-    if (int rc = toyni_air_program_check(insns, ninsns, &info)) return rc;
+    uint32_t nparams = 0;
+    if (int rc = air_program_check_impl(insns, ninsns, &info, with_params ? &nparams : nullptr)) return rc;
     std::vector<AirInsn> dev(ninsns);
     for (size_t k = 0; k < ninsns; ++k) {
         const toyni_air_insn& in = insns[k];
@@ -4787,6 +4891,7 @@ int toyni_air_program_create(toyni_ntt_ctx* c, const toyni_air_insn* insns, size
     toyni_air_program* p = new toyni_air_program();
     p->device = c->device;
     p->info = info;
+    p->nparams = nparams;
     hipError_t e = hipMalloc((void**)&p->d_insns, ninsns * sizeof(AirInsn));
     if (e == hipSuccess) e = hipMemcpy(p->d_insns, dev.data(), ninsns * sizeof(AirInsn), hipMemcpyHostToDevice);
     if (e != hipSuccess) {
@@ -4795,6 +4900,17 @@ int toyni_air_program_create(toyni_ntt_ctx* c, const toyni_air_insn* insns, size
         return (int)e;
     }
     *out = p;
+    return TOYNI_OK;
+}
+int toyni_air_program_create(toyni_ntt_ctx* c, const toyni_air_insn* insns, size_t ninsns, toyni_air_program** out) {
+    return air_program_create_impl(c, insns, ninsns, out, false);
+}
+int toyni_air_program_create_params(toyni_ntt_ctx* c, const toyni_air_insn* insns, size_t ninsns, toyni_air_program** out) {
+    return air_program_create_impl(c, insns, ninsns, out, true);
+}
+int toyni_air_program_nparams(const toyni_air_program* p, uint32_t* nparams) {
+    if (!p || !nparams) return TOYNI_E_NULL;
+    *nparams = p->nparams;
     return TOYNI_OK;
 }
 
@@ -4869,6 +4985,7 @@ int toyni_air_quotient_device(toyni_ntt_ctx* c, const toyni_air_program* prog, c
                               uint32_t shift, const uint32_t* weights, size_t nweights, uint32_t* d_c_out, uint32_t* d_q_out, int accumulate,
                               void* stream) {
     if (!c || !prog || !weights || !d_q_out || (!mats && nmats)) return TOYNI_E_NULL;
+    if (prog->nparams) return TOYNI_E_RANGE;   // a PARAM needs the parameter array of 3p
     if (int rc = air_quotient_check(c, prog, mats, nmats, log_blowup, shift, nweights, d_c_out, d_q_out)) return rc;
     for (size_t k = 0; k < nweights; ++k)
         if (weights[k] >= BB_P) return TOYNI_E_RANGE;
@@ -4904,6 +5021,7 @@ int toyni_air_quotient_ext_device(toyni_ntt_ctx* c, const toyni_air_program* pro
                                   uint32_t shift, const uint32_t* weights4, size_t nweights, uint32_t* d_c_out, uint32_t* d_q_out, size_t out_stride,
                                   int accumulate, void* stream) {
     if (!c || !prog || !weights4 || !d_q_out || (!mats && nmats)) return TOYNI_E_NULL;
+    if (prog->nparams) return TOYNI_E_RANGE;   // a PARAM needs the parameter array of 3p
     if (int rc = air_quotient_check(c, prog, mats, nmats, log_blowup, shift, nweights, d_c_out, d_q_out)) return rc;
     if (out_stride < ((size_t)1 << c->plan.log_n)) return TOYNI_E_RANGE;
     for (size_t k = 0; k < 4 * nweights; ++k)
@@ -4932,6 +5050,106 @@ int toyni_air_quotient_ext_device(toyni_ntt_ctx* c, const toyni_air_program* pro
     std::memcpy(h, weights4, words * sizeof(uint32_t));
     HIPCHK(hipMemcpyAsync(sc.d_lde32, h, words * sizeof(uint32_t), hipMemcpyHostToDevice, s));
     hipLaunchKernelGGL(air_quotient_ext_kernel, grid, dim3(shape.threads), (size_t)shape.lds_bytes, s, a, stride, (const uint32_t*)sc.d_lde32);
+    return (int)hipGetLastError();
+}
+
+// ---- section 3p: gamma and the constraint weights in device memory ----
+int toyni_air_quotient_ext_dc_device(toyni_ntt_ctx* c, const toyni_air_program* prog, const toyni_air_matrix* mats, size_t nmats, unsigned log_blowup,
+                                     uint32_t shift, const uint32_t* d_params, size_t nparams, const uint32_t* d_alphas, size_t nalphas,
+                                     int weights_form, uint32_t* d_c_out, uint32_t* d_q_out, size_t out_stride, int accumulate, void* stream) {
+    if (!c || !prog || !d_alphas || !d_q_out || (!mats && nmats) || (!d_params && nparams)) return TOYNI_E_NULL;
+    if (weights_form != TOYNI_AIR_WEIGHTS_EXT && weights_form != TOYNI_AIR_WEIGHTS_EMIT_EXT) return TOYNI_E_RANGE;
+    // (decided on the arguments alone, before the program or the context is read)
+    if (nparams > AIR_MAX_PARAMS || nalphas > AIR_DC_MAX_WEIGHTS || (((uintptr_t)d_params | (uintptr_t)d_alphas) & 3)) return TOYNI_E_RANGE;
+    if (nparams < prog->nparams) return TOYNI_E_RANGE;
+    const size_t nweights = air_dc_nweights((uint32_t)nalphas, (uint32_t)weights_form);
+    if (int rc = air_quotient_check(c, prog, mats, nmats, log_blowup, shift, nweights, d_c_out, d_q_out)) return rc;
+    if (out_stride < ((size_t)1 << c->plan.log_n)) return TOYNI_E_RANGE;
+    AirArgs a;
+    AirLaunchShape shape;
+    dim3 grid;
+    if (int rc = air_quotient_args(c, prog, mats, log_blowup, shift, d_c_out, d_q_out, accumulate, a, shape, grid)) return rc;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    // the stream's buffer holds the record; both launches are ordered by the stream, so the call is a chain of two kernels
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words, air_dc_record_words((uint32_t)nparams, (uint32_t)nalphas, (uint32_t)weights_form),
+                  sizeof(uint32_t));
+    if (rc) return rc;
+    uint32_t* rec = sc.d_lde32;
+    hipLaunchKernelGGL(air_dc_prepare_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, s, d_params, (uint32_t)nparams, d_alphas, (uint32_t)nalphas,
+                       (uint32_t)weights_form, rec);
+    hipLaunchKernelGGL(air_quotient_ext_dc_kernel, grid, dim3(shape.threads), (size_t)shape.lds_bytes, s, a, (uint64_t)out_stride,
+                       static_cast<const uint32_t*>(rec), (uint32_t)nparams);
+    return (int)hipGetLastError();
+}
+
+namespace {
+// ext_operand_ok for an operand whose shift is an index into the challenges; *index: what the preparation kernel reads
+bool ext_operand_dc_ok(const toyni_ext_operand_dc* o, size_t n, size_t batch, ExtAccumOperand* out, uint32_t* index) {
+    *out = ExtAccumOperand{};
+    *index = EXT_SHIFT_NONE;
+    if (!o || o->width == 0) return true;
+    if ((o->width != 1 && o->width != 4) || !o->d_values || ((uintptr_t)o->d_values & 3)) return false;
+    if ((o->width == 4 || batch > 1) && o->stride < n) return false;
+    if (o->shift_index != TOYNI_EXT_SHIFT_NONE && o->shift_index >= EXT_SHIFT_MAX_INDEX) return false;
+    out->values = o->d_values;
+    out->stride = o->stride;
+    out->width = o->width;
+    *index = o->shift_index;
+    return true;
+}
+}  // namespace
+
+int toyni_column_scan_ext_dc_device(toyni_ntt_ctx* c, const toyni_ext_operand_dc* num, const toyni_ext_operand_dc* den, const uint32_t* d_challenges,
+                                    uint32_t* d_out, size_t out_stride, size_t n, size_t batch, int op, const uint32_t* init, uint32_t* d_totals,
+                                    void* stream) {
+    // every refusal is decided on the arguments alone: the context is not touched before they have passed
+    if (!c || !d_out || !init) return TOYNI_E_NULL;
+    ExtAccumArgs a{};
+    uint32_t num_index, den_index;
+    if (!ext_operand_dc_ok(num, n, batch, &a.num, &num_index) || !ext_operand_dc_ok(den, n, batch, &a.den, &den_index) ||
+        (a.num.width == 0 && a.den.width == 0))
+        return TOYNI_E_RANGE;
+    if ((num_index != EXT_SHIFT_NONE || den_index != EXT_SHIFT_NONE) && !d_challenges) return TOYNI_E_NULL;
+    if ((op != TOYNI_SCAN_SUM && op != TOYNI_SCAN_PRODUCT) || n > ((size_t)1 << SCAN_MAX_LOG_N) || batch >= ((size_t)1 << 14) || out_stride < n ||
+        (((uintptr_t)d_out | (uintptr_t)d_totals | (uintptr_t)d_challenges) & 3))
+        return TOYNI_E_RANGE;
+    for (size_t w = 0; w < 4 * batch; ++w)
+        if (init[w] >= BB_P) return TOYNI_E_RANGE;
+    if (batch == 0 || n == 0) return TOYNI_OK;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    a.out_stride = out_stride;
+    a.n = n;
+    a.ntiles = (uint32_t)((n + EXT_ACCUM_TILE - 1) / EXT_ACCUM_TILE);
+    a.single = a.ntiles == 1 ? 1u : 0u;
+    // the stream's buffer: the tile words of one launch sequence's columns (none for a single tile), then the record, 16-byte aligned
+    const size_t tile_words = a.single ? 0 : (size_t)EXT_ACCUM_TILE_WORDS * a.ntiles * std::min<size_t>(batch, EXT_ACCUM_INLINE_COLUMNS);
+    const size_t rec_at = (tile_words + 3) & ~(size_t)3;
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words, rec_at + sizeof(ExtAccumRecord) / sizeof(uint32_t), sizeof(uint32_t));
+    if (rc) return rc;
+    a.tiles = a.single ? nullptr : sc.d_lde32;
+    ExtAccumRecord* rec = reinterpret_cast<ExtAccumRecord*>(sc.d_lde32 + rec_at);
+    hipLaunchKernelGGL(extcol_dc_prepare_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, s, d_challenges, num_index, den_index,
+                       a.den.width == 1 ? 1u : 0u, rec);
+    // one record serves every launch sequence of the call
+    const ExtAccumOperand num0 = a.num, den0 = a.den;
+    for (size_t b0 = 0; b0 < batch; b0 += EXT_ACCUM_INLINE_COLUMNS) {
+        const unsigned cols = (unsigned)std::min<size_t>(batch - b0, EXT_ACCUM_INLINE_COLUMNS);
+        ExtAccumSeeds in{};
+        for (unsigned b = 0; b < cols; ++b)
+            for (int k = 0; k < 4; ++k) in.v[b][k] = op == TOYNI_SCAN_PRODUCT ? to_mont_host(init[4 * (b0 + b) + k]) : init[4 * (b0 + b) + k];
+        a.num.values = num0.values ? num0.values + b0 * num0.width * num0.stride : nullptr;
+        a.den.values = den0.values ? den0.values + b0 * den0.width * den0.stride : nullptr;
+        a.out = d_out + 4 * b0 * out_stride;
+        a.totals = d_totals ? d_totals + 8 * b0 : nullptr;
+        if (op == TOYNI_SCAN_PRODUCT) ext_accum_dc_launch<SCAN_PRODUCT>(a, in, static_cast<const ExtAccumRecord*>(rec), cols, s);
+        else ext_accum_dc_launch<SCAN_SUM>(a, in, static_cast<const ExtAccumRecord*>(rec), cols, s);
+    }
     return (int)hipGetLastError();
 }
 

@@ -196,6 +196,7 @@ def query_rows_device(d_indices: int, count: int, n: int, offsets, d_out: int, s
 
 # ---- constraint programs (include/toyni_hip.h 3f) ----
 AIR_CELL, AIR_CONST, AIR_X, AIR_XINV, AIR_ADD, AIR_SUB, AIR_MUL, AIR_EMIT = range(8)
+AIR_PARAM, AIR_MAX_PARAMS = 8, 256   # include/toyni_hip.h 3p: r[dst] = params[imm], a value the program does not carry
 AIR_MAX_REGS, AIR_MAX_MATRICES = 64, 4
 _P = 2013265921
 
@@ -226,16 +227,32 @@ def air_program_check(insns) -> AirInfo:
     return info
 
 
-class AirProgram:
-    """A validated constraint program on ctx's device (toyni_air_program_create); a context manager."""
+def air_program_check_params(insns):
+    """toyni_air_program_check_params: the same check with AIR_PARAM accepted.  -> (AirInfo, nparams)"""
+    arr = insns if isinstance(insns, ctypes.Array) else air_insns(insns)
+    info, nparams = AirInfo(), ctypes.c_uint32()
+    check(lib.toyni_air_program_check_params(arr if len(arr) else None, len(arr), ctypes.byref(info), ctypes.byref(nparams)),
+          "constraint program refused")
+    return info, nparams.value
 
-    def __init__(self, ctx, insns):
+
+class AirProgram:
+    """A validated constraint program on ctx's device (toyni_air_program_create); a context manager.  params=True:
+    toyni_air_program_create_params, which accepts AIR_PARAM; such a program runs under air_quotient_ext_dc_device."""
+
+    def __init__(self, ctx, insns, params=False):
         arr = insns if isinstance(insns, ctypes.Array) else air_insns(insns)
         h = ctypes.c_void_p()
-        check(lib.toyni_air_program_create(ctx.handle, arr if len(arr) else None, len(arr), ctypes.byref(h)), "constraint program refused")
+        create = lib.toyni_air_program_create_params if params else lib.toyni_air_program_create
+        check(create(ctx.handle, arr if len(arr) else None, len(arr), ctypes.byref(h)), "constraint program refused")
         self.handle = h
         self.info = AirInfo()
         check(lib.toyni_air_program_info(h, ctypes.byref(self.info)), "constraint program info failed")
+        self.nparams = 0
+        if params:
+            n = ctypes.c_uint32()
+            check(lib.toyni_air_program_nparams(h, ctypes.byref(n)), "constraint program info failed")
+            self.nparams = n.value
 
     def destroy(self) -> None:
         if self.handle:
@@ -274,6 +291,21 @@ def air_quotient_ext_device(ctx, prog, mats, log_blowup: int, shift: int, weight
     check(lib.toyni_air_quotient_ext_device(ctx.handle, prog.handle, m if len(mats) else None, len(mats), log_blowup, shift, w.ctypes.data, w.size // 4,
                                             d_c_out or None, d_q_out, out_stride, 1 if accumulate else 0, stream or None),
           "GPU constraint program under Ext weights failed")
+
+
+AIR_WEIGHTS_EXT, AIR_WEIGHTS_EMIT_EXT = 0, 1
+
+
+def air_quotient_ext_dc_device(ctx, prog, mats, log_blowup: int, shift: int, d_params: int, nparams: int, d_alphas: int, nalphas: int,
+                               weights_form: int, d_q_out: int, out_stride: int, d_c_out: int = 0, accumulate: bool = False, stream=None) -> None:
+    """air_quotient_ext_device with the parameters of an AirProgram(params=True) and the weights in device memory (include/toyni_hip.h
+    3p).  d_params: nparams words; d_alphas: nalphas Ext elements.  AIR_WEIGHTS_EXT: the alphas are the weights; AIR_WEIGHTS_EMIT_EXT:
+    alpha_k weighs the four base constraints of emit_ext constraint k (what air_ext_weights builds on the host).  Two launches, nothing
+    read back: the call only enqueues."""
+    m = (AirMatrix * len(mats))(*[AirMatrix(d or None, w, cs) for d, w, cs in mats])
+    check(lib.toyni_air_quotient_ext_dc_device(ctx.handle, prog.handle, m if len(mats) else None, len(mats), log_blowup, shift, d_params or None,
+                                               nparams, d_alphas or None, nalphas, weights_form, d_c_out or None, d_q_out, out_stride,
+                                               1 if accumulate else 0, stream or None), "GPU constraint program under device challenges failed")
 
 
 def air_ext_weights(alphas):
@@ -330,6 +362,12 @@ class AirBuilder:
     def x(self): return self._node((AIR_X,))
     def xinv(self, v): return self._node((AIR_XINV, int(v) % _P))
 
+    def param(self, j):
+        """params[j] of air_quotient_ext_dc_device (include/toyni_hip.h 3p): a value the call reads from device memory."""
+        if not 0 <= int(j) < AIR_MAX_PARAMS:
+            raise ValueError("a parameter index is below 256")
+        return self._node((AIR_PARAM, int(j)))
+
     def emit(self, k, expr, divide=True):
         self.emits.append((int(k), expr if isinstance(expr, AirExpr) else self.const(expr), bool(divide)))
 
@@ -376,7 +414,7 @@ class AirBuilder:
             op = what.key[0]
             if op == AIR_CELL:
                 insns.append((op, dst, what.key[3], what.key[1], what.key[2]))
-            elif op in (AIR_CONST, AIR_XINV):
+            elif op in (AIR_CONST, AIR_XINV, AIR_PARAM):
                 insns.append((op, dst, 0, 0, what.key[1]))
             elif op == AIR_X:
                 insns.append((op, dst, 0, 0, 0))
@@ -397,6 +435,10 @@ class AirBuilder:
         v = [int(c) for c in v4]
         assert len(v) == 4
         return AirExt(tuple(self.const(c) for c in v))
+
+    def ext_param(self, first):
+        """The Ext value held in the parameters first .. first + 3: usable wherever ext_const is."""
+        return AirExt(tuple(self.param(int(first) + k) for k in range(4)))
 
     def ext(self, e):
         """An Ext expression from an AirExt (itself), a base-field AirExpr or an int (embedded in coordinate 0)."""
@@ -526,6 +568,32 @@ def column_scan_ext_device(ctx, num, den, out: int, out_stride: int, n: int, bat
     assert i.size == 4 * batch
     check(lib.toyni_column_scan_ext_device(ctx.handle, ctypes.byref(num) if num is not None else None, ctypes.byref(den) if den is not None else None,
                                            out, out_stride, n, batch, op, i.ctypes.data, totals or None, stream or None), "GPU Ext column scan failed")
+
+
+# ---- the same with gamma in device memory (include/toyni_hip.h 3p) ----
+EXT_SHIFT_NONE = 0xFFFFFFFF
+
+
+class _ExtOperandDc(ctypes.Structure):   # toyni_ext_operand_dc
+    _fields_ = [("d_values", ctypes.c_void_p), ("stride", ctypes.c_size_t), ("width", ctypes.c_uint32), ("shift_index", ctypes.c_uint32)]
+
+
+def ExtOperandDc(d_values: int = 0, stride: int = 0, width: int = 0, shift_index: int = EXT_SHIFT_NONE) -> _ExtOperandDc:
+    """ExtOperand whose shift is the Ext element number shift_index of the call's d_challenges (EXT_SHIFT_NONE: no shift)."""
+    return _ExtOperandDc(d_values or None, stride, width, shift_index)
+
+
+def column_scan_ext_dc_device(ctx, num, den, d_challenges: int, out: int, out_stride: int, n: int, batch: int = 1, op: int = SCAN_SUM, init=None,
+                              totals: int = 0, stream=None) -> None:
+    """column_scan_ext_device with the operands' shifts read from device memory: num, den are ExtOperandDc or None.  The call only
+    enqueues; the words are reduced mod p on the device."""
+    if init is None:
+        init = [[1 if op == SCAN_PRODUCT else 0, 0, 0, 0]] * batch
+    i = np.ascontiguousarray(init, dtype=np.uint32)
+    assert i.size == 4 * batch
+    check(lib.toyni_column_scan_ext_dc_device(ctx.handle, ctypes.byref(num) if num is not None else None, ctypes.byref(den) if den is not None else None,
+                                              d_challenges or None, out, out_stride, n, batch, op, i.ctypes.data, totals or None, stream or None),
+          "GPU Ext column scan under device challenges failed")
 
 
 # ---- the Fiat-Shamir transcript in device memory and the commit phases on it (include/toyni_hip.h 3l) ----
