@@ -905,6 +905,58 @@ int toyni_column_scan_ext_dc_device(toyni_ntt_ctx* ctx, const toyni_ext_operand_
                                     const uint32_t* init, uint32_t* d_totals, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * 3q. The base-field first half of a Fibonacci proof (the reference's own protocol, src/fibonacci.rs:99-310) without the host: the
+ *     mask, derive_z, the out-of-domain values, the constraint check at z and the DEEP layer of 3c with z and the claimed values read
+ *     from DEVICE memory.  Together with 3l and 3o the sequence
+ *         upload, INTT -> toyni_mask_poly_device -> LDE, trees, quotient (3c) -> toyni_transcript_absorb_device (both roots)
+ *         -> toyni_transcript_squeeze_point_device -> toyni_poly_eval_dz_device (T at z, g z, g^2 z; Q at z, into one buffer)
+ *         -> toyni_transcript_absorb_fields_device -> toyni_fib_deep_dz_device -> toyni_merkle_commit_device, absorb
+ *         -> toyni_fri_commit_phase_transcript_device -> toyni_transcript_squeeze_indices_device
+ *         -> toyni_fri_query_positions_device, toyni_query_rows_device -> toyni_merkle_open_groups_device
+ *         -> toyni_fri_phase_roots_device -> one download
+ *     only enqueues (csrc/host/fib_prover_dt.hpp is that caller).  Conventions of 3o / 3p: asynchronous on `stream`, packed-u32 words,
+ *     no environment variable, no callback, no host read; refusals on the host before anything is enqueued, the outputs untouched;
+ *     every field word read from device memory is reduced mod p by the one-wave kernel that first touches it, and the result is that
+ *     of the host-argument call on the reduced values; the transcript's `status` is sticky (3l); on a warm context each call is a
+ *     linear chain of kernels and can be captured into a HIP graph (caveat of section 4).  No existing entry point, record layout or
+ *     written byte changes.
+ * ---------------------------------------------------------------------------------------------- */
+/* T_hat = T - R + x^n R in place on d_coeffs[0 .. n + mask_degree): R_i = (the little-endian u64 of keystream words 2 i, 2 i + 1) mod p
+ * of the ChaCha20 stream of toyni_chacha20_fill_device under key / nonce (block i / 8), i < mask_degree.  One launch, one thread per
+ * OUTPUT word: R_j is subtracted where j < mask_degree and R_(j - n) added where n <= j < n + mask_degree, so the overlapping case
+ * n < mask_degree has no two threads on one word.  Words outside the two ranges are not touched; the touched ones are reduced.
+ * TOYNI_E_NULL for a null d_coeffs or key; TOYNI_E_RANGE for mask_degree == 0, mask_degree > 4096, n == 0 or a d_coeffs that is not
+ * 4-byte aligned. */
+int toyni_mask_poly_device(uint32_t* d_coeffs, size_t n, unsigned mask_degree, const uint8_t key[32], uint64_t nonce, void* stream);
+/* derive_z_from_transcript (src/fibonacci.rs:379-399): one challenge, squeezed again while z^N == 1 or (z / shift)^N == 1, N = 2^log_N
+ * (z on the trace domain's extension or on the LDE coset); d_z receives the one word.  One launch of one wave, log_N squarings per
+ * test.  At most 8 tries: after the eighth rejection d_z is zero, the state stays as it was and status = TOYNI_E_RANGE.  A transcript
+ * whose status is set writes zero.  TOYNI_E_NULL for a null pointer; TOYNI_E_RANGE for log_N > 27, shift == 0, shift >= p, a d_tr that
+ * is not 16-byte or a d_z that is not 4-byte aligned. */
+int toyni_transcript_squeeze_point_device(toyni_transcript* d_tr, unsigned log_N, uint32_t shift, uint32_t* d_z, void* stream);
+/* toyni_poly_eval_device at the points mults[p] * z: z is one word of device memory, mults a host array of npoints canonical
+ * multipliers (1, g, g^2).  Three launches: a one-wave kernel writes z, z^16 and z^4096 of every point (Montgomery forms) into a
+ * record behind the partial sums in the context's per-stream buffer, then twins of the two stages read the record.  The output bytes
+ * are those of the host-point call; ncoeffs == 0 writes zeros.  Refusals are those of the host-point call, with "a point >= p" read
+ * as "a multiplier >= p", a null d_z (TOYNI_E_NULL) and a d_coeffs, d_z or d_out that is not 4-byte aligned (TOYNI_E_RANGE). */
+int toyni_poly_eval_dz_device(toyni_ntt_ctx* ctx, const uint32_t* d_coeffs, size_t ncoeffs, const uint32_t* d_z, const uint32_t* mults,
+                              unsigned npoints, uint32_t* d_out, void* stream);
+/* toyni_fib_deep_device with z (d_z, one word) and the claimed values (d_ood = {t_z, t_gz, t_ggz, q_z}) in device memory.  Two
+ * launches: a one-wave kernel writes the record the layer kernel's twin reads.  If d_check is not NULL that kernel also evaluates the
+ * prover's own check (src/fibonacci.rs:173-177) with n = trace_len (a power of two <= 2^27) and g the root of unity of order n:
+ *     d_check[0] = 1 if (t_ggz - t_gz - t_z)(z - g^(n-1))(z - g^(n-2)) == q_z (z^n - 1), else 0.
+ * The output bytes are those of toyni_fib_deep_device on the reduced values, the x_i = z rule and the N < 8 path included.
+ * Refusals: those of toyni_fib_deep_device that do not concern a host value; TOYNI_E_NULL for a null d_z or d_ood; TOYNI_E_RANGE for
+ * a trace_len that is not a power of two or exceeds 2^27, or a d_z, d_ood or d_check that is not 4-byte aligned. */
+int toyni_fib_deep_dz_device(toyni_ntt_ctx* ctx, const uint32_t* d_trace_lde, const uint32_t* d_q_evals, uint32_t* d_out, unsigned log_blowup,
+                             uint32_t shift, const uint32_t* d_z, const uint32_t* d_ood, uint32_t trace_len, uint32_t* d_check, void* stream);
+/* The roots of the trees a commit phase of 3l / 3m left back to back in d_levels: tree k = 0 .. rounds - 1 has m_first >> k leaves
+ * (for toyni_fri_commit_phase_transcript_device m_first = m0 / 2); its root goes to d_roots[32 k ..].  One launch.  rounds == 0 enqueues
+ * nothing.  TOYNI_E_NULL for a null pointer; TOYNI_E_INVALID_SIZE for an m_first that is not a power of two or exceeds 2^32;
+ * TOYNI_E_RANGE for rounds > 64, m_first >> (rounds - 1) == 0, a d_levels that is not 16-byte or a d_roots that is not 4-byte aligned. */
+int toyni_fri_phase_roots_device(const uint8_t* d_levels, size_t m_first, unsigned rounds, uint8_t* d_roots, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:
  *     src/fibonacci.rs:133-150,186-198,222-245, src/math/polynomial.rs:134-144, src/merkle.rs:50-80).  All asynchronous on
  *     `stream`; packed u32 device data; ctx = a context of size N = the LDE size (its domain table supplies x_i = shift w_N^i).

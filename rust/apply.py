@@ -24,7 +24,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-HIP_SOURCES = ["toyni_hip.hip", "ntt_kernels.hpp", "ntt_plan.hpp", "ntt_route.hpp", "bb_field.hpp", "merkle_kernels.hpp", "prover_kernels.hpp", "transcript_kernels.hpp", "pow_kernels.hpp", "dz_kernels.hpp", "dc_kernels.hpp", "multi_gpu.hpp"]
+HIP_SOURCES = ["toyni_hip.hip", "ntt_kernels.hpp", "ntt_plan.hpp", "ntt_route.hpp", "bb_field.hpp", "merkle_kernels.hpp", "prover_kernels.hpp", "transcript_kernels.hpp", "pow_kernels.hpp", "dz_kernels.hpp", "dc_kernels.hpp", "fib_dz_kernels.hpp", "multi_gpu.hpp"]
 
 
 def matching_brace(src: str, open_at: int) -> int:

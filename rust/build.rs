@@ -31,6 +31,7 @@ fn main() {
     println!("cargo:rerun-if-changed=hip/pow_kernels.hpp");
     println!("cargo:rerun-if-changed=hip/dz_kernels.hpp");
     println!("cargo:rerun-if-changed=hip/dc_kernels.hpp");
+    println!("cargo:rerun-if-changed=hip/fib_dz_kernels.hpp");
     println!("cargo:rerun-if-changed=hip/toyni_hip.h");
     println!("cargo::rustc-check-cfg=cfg(has_hip)");
     if env::var_os("CARGO_FEATURE_HIP").is_none() {

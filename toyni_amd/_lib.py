@@ -175,6 +175,12 @@ SIGNATURES = {
                                                  c_void_p, c_void_p, c_size, c_int, c_void_p]),
     "toyni_column_scan_ext_dc_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size, c_size, c_size, c_int, c_void_p, c_void_p,
                                                 c_void_p]),
+    # section 3q
+    "toyni_mask_poly_device": (c_int, [c_void_p, c_size, ctypes.c_uint, c_void_p, c_u64, c_void_p]),
+    "toyni_transcript_squeeze_point_device": (c_int, [c_void_p, ctypes.c_uint, c_u32, c_void_p, c_void_p]),
+    "toyni_poly_eval_dz_device": (c_int, [c_void_p, c_void_p, c_size, c_void_p, c_void_p, ctypes.c_uint, c_void_p, c_void_p]),
+    "toyni_fib_deep_dz_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint, c_u32, c_void_p, c_void_p, c_u32, c_void_p, c_void_p]),
+    "toyni_fri_phase_roots_device": (c_int, [c_void_p, c_size, ctypes.c_uint, c_void_p, c_void_p]),
     # section 3c
     "toyni_fri_fold_commit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

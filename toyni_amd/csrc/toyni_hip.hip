@@ -29,6 +29,7 @@
 #include "pow_kernels.hpp"
 #include "dz_kernels.hpp"
 #include "dc_kernels.hpp"
+#include "fib_dz_kernels.hpp"
 
 using namespace toyni;
 
@@ -1803,6 +1804,85 @@ __global__ void __launch_bounds__(EXT_ACCUM_THREADS) extcol_apply_dc_kernel(cons
     ExtAccumArgs b = a;
     ext_accum_args_from_record(b, *rec);
     ext_accum_apply_body<OP>(b, in, wave_tot, wave_zeros);
+}
+
+// ---- the base-field first half of a Fibonacci proof without the host (fib_dz_kernels.hpp; include/toyni_hip.h 3q) ----
+// One-wave preparation kernels again, and twins of the three hot kernels of 3c that read z (and the claimed values) from the record
+// the preparation left in the stream's buffer.  The argument-fed kernels above are not touched.
+__global__ void __launch_bounds__(256) fib_mask_kernel(const FibMaskArgs a) {
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= fib_mask_items(a.n, a.mask_degree)) return;
+    const uint64_t j = fib_mask_item_word(a.n, a.mask_degree, t);
+    a.coeffs[j] = fib_mask_output(a, j, a.coeffs[j]);
+}
+__global__ void __launch_bounds__(TRANSCRIPT_T) transcript_squeeze_point_kernel(TranscriptState* __restrict__ tr, uint32_t log_N, uint32_t shift_invR,
+                                                                                 uint32_t* __restrict__ z) {
+    if (threadIdx.x == 0) transcript_squeeze_point(*tr, log_N, shift_invR, FIB_POINT_TRIES, z);
+}
+// lane p: the three powers of point mults[p] * z
+__global__ void __launch_bounds__(TRANSCRIPT_T) poly_dz_prepare_kernel(const uint32_t* __restrict__ z, const PolyDzMults mults, uint32_t npoints,
+                                                                       PolyDzRecord* __restrict__ rec) {
+    if (threadIdx.x < npoints) poly_dz_record_point(z, mults.v[threadIdx.x], threadIdx.x, *rec);
+}
+__global__ void __launch_bounds__(256) poly_eval_partial_dz_kernel(const PolyEvalDzArgs a, const PolyDzRecord* __restrict__ rec) {
+    __shared__ uint32_t red[256];
+    const uint64_t base = (uint64_t)blockIdx.x * POLY_CHUNK + (uint64_t)threadIdx.x * POLY_PER_THREAD;
+    uint32_t c[POLY_PER_THREAD];
+#pragma unroll
+    for (uint32_t j = 0; j < POLY_PER_THREAD; ++j) c[j] = base + j < a.ncoeffs ? a.coeffs[base + j] : 0u;
+    for (uint32_t p = 0; p < a.npoints; ++p) {
+        const uint32_t sum = block_sum_mod(poly_thread_term(poly_dz_point_args(rec, p), 0u, c, threadIdx.x), red);
+        if (threadIdx.x == 0) a.partial[(uint64_t)blockIdx.x * a.npoints + p] = sum;
+    }
+}
+__global__ void __launch_bounds__(256) poly_eval_final_dz_kernel(const PolyEvalDzArgs a, const PolyDzRecord* __restrict__ rec) {
+    __shared__ uint32_t red[256];
+    for (uint32_t p = 0; p < a.npoints; ++p) {
+        const uint32_t zchunkR = TOYNI_UNIFORM_LOAD(&rec->zchunkR[p]);
+        uint32_t acc = 0;
+        for (uint32_t b = threadIdx.x; b < a.nblocks; b += blockDim.x)
+            acc = bb_add(acc, mont_mul(a.partial[(uint64_t)b * a.npoints + p], mont_pow(zchunkR, b)));
+        const uint32_t sum = block_sum_mod(acc, red);
+        if (threadIdx.x == 0) a.out[p] = sum;
+    }
+}
+__global__ void __launch_bounds__(TRANSCRIPT_T) fib_deep_prepare_kernel(const uint32_t* __restrict__ z, const uint32_t* __restrict__ ood, const FibCheckArgs k,
+                                                                        FibDeepRecord* __restrict__ rec, uint32_t* __restrict__ check) {
+    if (threadIdx.x == 0) fib_deep_prepare(z, ood, k, rec, check);
+}
+// fib_deep_kernel with z and the claimed values from the record
+__global__ void __launch_bounds__(256) fib_deep_dz_kernel(const DeepArgs in, const FibDeepRecord* __restrict__ rec) {
+    constexpr int K = 8;
+    DeepArgs a = in;
+    fib_deep_args_from_record(a, *rec);
+    const uint64_t N = (uint64_t)1 << a.log_N, mask = N - 1, B = (uint64_t)1 << a.log_blowup;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    if (a.log_N >= 3) {
+        for (uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; g < N / K; g += stride) {
+            const uint64_t i0 = g * K;
+            uint32_t t0[K], t1[K], t2[K], qv[K], out[K];
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                t0[j] = a.trace[i0 + j];
+                t1[j] = a.trace[(i0 + j + B) & mask];
+                t2[j] = a.trace[(i0 + j + 2 * B) & mask];
+                qv[j] = a.quot[i0 + j];
+            }
+            deep_group<K>(a, i0, t0, t1, t2, qv, out);
+#pragma unroll
+            for (int j = 0; j < K; ++j) a.out[i0 + j] = out[j];
+        }
+    } else {
+        for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += stride) {
+            const uint32_t t0[1] = {a.trace[i]}, t1[1] = {a.trace[(i + B) & mask]}, t2[1] = {a.trace[(i + 2 * B) & mask]}, qv[1] = {a.quot[i]};
+            uint32_t out[1];
+            deep_group<1>(a, i, t0, t1, t2, qv, out);
+            a.out[i] = out[0];
+        }
+    }
+}
+__global__ void __launch_bounds__(256) fri_phase_roots_kernel(const uint32_t* __restrict__ levels, uint64_t m_first, uint32_t rounds, uint32_t* __restrict__ roots) {
+    for (uint32_t t = threadIdx.x; t < 8u * rounds; t += blockDim.x) roots[t] = fri_phase_root_word(levels, m_first, t);
 }
 
 // ---- a proof-of-work nonce on that transcript (pow_kernels.hpp; include/toyni_hip.h 3n) ----
@@ -4673,6 +4753,108 @@ int toyni_deep_combine_ext_dz_device(toyni_ntt_ctx* c, const uint32_t* d_values,
     }
     const uint64_t items = log_N >= 2 ? N / 4 : N;
     hipLaunchKernelGGL(deep_combine_ext_dz_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, a, static_cast<const DeepExtRecord*>(rec));
+    return (int)hipGetLastError();
+}
+
+// ---- section 3q: the base-field first half of a Fibonacci proof with z in device memory ----
+int toyni_mask_poly_device(uint32_t* d_coeffs, size_t n, unsigned mask_degree, const uint8_t key[32], uint64_t nonce, void* stream) {
+    if (!d_coeffs || !key) return TOYNI_E_NULL;
+    if (mask_degree == 0 || mask_degree > FIB_MASK_MAX_DEGREE || n == 0 || ((uintptr_t)d_coeffs & 3)) return TOYNI_E_RANGE;
+    FibMaskArgs a{};
+    a.coeffs = d_coeffs;
+    a.n = n;
+    a.mask_degree = mask_degree;
+    std::memcpy(a.key, key, 32);
+    a.nonce[0] = 0u;
+    a.nonce[1] = (uint32_t)nonce;
+    a.nonce[2] = (uint32_t)(nonce >> 32);
+    const uint64_t items = fib_mask_items(n, mask_degree);   // <= 2 x 4096: the grid is never capped
+    hipLaunchKernelGGL(fib_mask_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    return (int)hipGetLastError();
+}
+
+int toyni_transcript_squeeze_point_device(toyni_transcript* d_tr, unsigned log_N, uint32_t shift, uint32_t* d_z, void* stream) {
+    if (!d_tr || !d_z) return TOYNI_E_NULL;
+    if (((uintptr_t)d_tr & 15) || ((uintptr_t)d_z & 3) || log_N > FIB_POINT_MAX_LOG_N || shift == 0 || shift >= BB_P) return TOYNI_E_RANGE;
+    hipLaunchKernelGGL(transcript_squeeze_point_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, (hipStream_t)stream, transcript_of(d_tr), (uint32_t)log_N,
+                       to_mont_host(bb_inv_host(shift)), d_z);
+    return (int)hipGetLastError();
+}
+
+int toyni_poly_eval_dz_device(toyni_ntt_ctx* c, const uint32_t* d_coeffs, size_t ncoeffs, const uint32_t* d_z, const uint32_t* mults, unsigned npoints,
+                              uint32_t* d_out, void* stream) {
+    if (!c || !d_z || !mults || !d_out || (!d_coeffs && ncoeffs)) return TOYNI_E_NULL;
+    if (npoints < 1 || npoints > (unsigned)POLY_MAX_POINTS) return TOYNI_E_RANGE;
+    PolyDzMults m{};
+    for (unsigned p = 0; p < npoints; ++p) {
+        if (mults[p] >= BB_P) return TOYNI_E_RANGE;
+        m.v[p] = mults[p];
+    }
+    if (((uintptr_t)d_coeffs | (uintptr_t)d_out | (uintptr_t)d_z) & 3) return TOYNI_E_RANGE;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    if (ncoeffs == 0) return (int)hipMemsetAsync(d_out, 0, npoints * sizeof(uint32_t), s);   // the zero polynomial
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    PolyEvalDzArgs a{};
+    a.coeffs = d_coeffs;
+    a.ncoeffs = ncoeffs;
+    a.npoints = npoints;
+    a.nblocks = (uint32_t)((ncoeffs + POLY_CHUNK - 1) / POLY_CHUNK);
+    // the stream's buffer: the partial sums, rounded up to a multiple of four words, then the record
+    const size_t partial_words = ((size_t)a.nblocks * npoints + 3) & ~(size_t)3;
+    int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words, partial_words + sizeof(PolyDzRecord) / sizeof(uint32_t), sizeof(uint32_t));
+    if (rc) return rc;
+    a.partial = sc.d_lde32;
+    a.out = d_out;
+    PolyDzRecord* rec = reinterpret_cast<PolyDzRecord*>(sc.d_lde32 + partial_words);
+    hipLaunchKernelGGL(poly_dz_prepare_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, s, d_z, m, (uint32_t)npoints, rec);
+    hipLaunchKernelGGL(poly_eval_partial_dz_kernel, dim3(a.nblocks), dim3(POLY_THREADS), 0, s, a, static_cast<const PolyDzRecord*>(rec));
+    hipLaunchKernelGGL(poly_eval_final_dz_kernel, dim3(1), dim3(256), 0, s, a, static_cast<const PolyDzRecord*>(rec));
+    return (int)hipGetLastError();
+}
+
+int toyni_fib_deep_dz_device(toyni_ntt_ctx* c, const uint32_t* d_trace_lde, const uint32_t* d_q_evals, uint32_t* d_out, unsigned log_blowup,
+                             uint32_t shift, const uint32_t* d_z, const uint32_t* d_ood, uint32_t trace_len, uint32_t* d_check, void* stream) {
+    if (!c || !d_trace_lde || !d_q_evals || !d_out || !d_z || !d_ood) return TOYNI_E_NULL;
+    // decided on the arguments alone, before the context is read
+    if (shift == 0 || shift >= BB_P || !is_pow2(trace_len) || trace_len > (1u << 27) || (((uintptr_t)d_z | (uintptr_t)d_ood | (uintptr_t)d_check) & 3))
+        return TOYNI_E_RANGE;
+    const int log_N = c->plan.log_n;
+    if ((int)log_blowup > log_N) return TOYNI_E_RANGE;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    hipStream_t s = (hipStream_t)stream;
+    DeepArgs a{};
+    a.trace = d_trace_lde;
+    a.quot = d_q_evals;
+    a.out = d_out;
+    a.dom = domain_args(c, (unsigned)log_N, shift);
+    a.log_N = (uint32_t)log_N;
+    a.log_blowup = log_blowup;
+    a.wNR = to_mont_host(bb_root_of_unity_host((uint32_t)log_N));
+    FibCheckArgs k{};
+    k.log_n = (uint32_t)ilog2(trace_len);
+    const uint32_t g_inv = bb_inv_host(bb_root_of_unity_host(k.log_n));   // g^(n-1) = g^-1, g^(n-2) = g^-2
+    k.b1R = to_mont_host(g_inv);
+    k.b2R = to_mont_host(bb_mul_host(g_inv, g_inv));
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words, sizeof(FibDeepRecord) / sizeof(uint32_t), sizeof(uint32_t));
+    if (rc) return rc;
+    FibDeepRecord* rec = reinterpret_cast<FibDeepRecord*>(sc.d_lde32);
+    hipLaunchKernelGGL(fib_deep_prepare_kernel, dim3(1), dim3(TRANSCRIPT_T), 0, s, d_z, d_ood, k, rec, d_check);
+    const uint64_t items = log_N >= 3 ? (1ull << log_N) / 8 : (1ull << log_N);
+    hipLaunchKernelGGL(fib_deep_dz_kernel, dim3(grid_for(items)), dim3(256), 0, s, a, static_cast<const FibDeepRecord*>(rec));
+    return (int)hipGetLastError();
+}
+
+int toyni_fri_phase_roots_device(const uint8_t* d_levels, size_t m_first, unsigned rounds, uint8_t* d_roots, void* stream) {
+    if (!d_levels || !d_roots) return TOYNI_E_NULL;
+    if (!is_pow2(m_first) || (uint64_t)m_first > ((uint64_t)1 << 32)) return TOYNI_E_INVALID_SIZE;
+    if (rounds > FRI_PHASE_MAX_ROUNDS || (rounds && (m_first >> (rounds - 1)) == 0) || ((uintptr_t)d_levels & 15) || ((uintptr_t)d_roots & 3)) return TOYNI_E_RANGE;
+    if (rounds == 0) return TOYNI_OK;
+    hipLaunchKernelGGL(fri_phase_roots_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const uint32_t*>(d_levels), (uint64_t)m_first,
+                       (uint32_t)rounds, reinterpret_cast<uint32_t*>(d_roots));
     return (int)hipGetLastError();
 }
 

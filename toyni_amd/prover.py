@@ -194,6 +194,33 @@ def query_rows_device(d_indices: int, count: int, n: int, offsets, d_out: int, s
     check(lib.toyni_query_rows_device(d_indices or None, count, n, off.ctypes.data, off.size, d_out or None, stream or None), "GPU query rows failed")
 
 
+# ---- the base-field first half of a Fibonacci proof with z in device memory (include/toyni_hip.h 3q) ----
+def mask_poly_device(d_coeffs: int, n: int, mask_degree: int, key: bytes, nonce: int = 1, stream: int = 0) -> None:
+    """T_hat = T - R + x^n R in place on d_coeffs[0 .. n + mask_degree); R from the ChaCha20 keystream under (key, nonce)."""
+    k = (ctypes.c_uint8 * 32).from_buffer_copy(bytes(key)) if key is not None else None
+    check(lib.toyni_mask_poly_device(d_coeffs or None, n, mask_degree, k, nonce, stream or None), "GPU mask failed")
+
+
+def poly_eval_dz_device(ctx, d_coeffs: int, ncoeffs: int, d_z: int, mults, d_out: int, stream: int = 0) -> None:
+    """poly_eval_device at the points mults[p] * z, z one word at the device pointer d_z; mults: canonical multipliers (1, g, g^2)."""
+    m = np.ascontiguousarray(mults, dtype=np.uint32).ravel()
+    check(lib.toyni_poly_eval_dz_device(ctx.handle, d_coeffs or None, ncoeffs, d_z or None, m.ctypes.data, m.size, d_out or None, stream or None),
+          "GPU polynomial evaluation (device point) failed")
+
+
+def fib_deep_dz_device(ctx, d_trace_lde: int, d_q_evals: int, d_out: int, log_blowup: int, shift: int, d_z: int, d_ood: int, trace_len: int,
+                       d_check: int = 0, stream: int = 0) -> None:
+    """fib_deep_device with z (d_z) and {t_z, t_gz, t_ggz, q_z} (d_ood) in device memory; d_check (optional): one word that
+    receives 1 where the constraint check at z holds for a trace of trace_len rows, else 0."""
+    check(lib.toyni_fib_deep_dz_device(ctx.handle, d_trace_lde, d_q_evals, d_out, log_blowup, shift, d_z or None, d_ood or None, trace_len,
+                                       d_check or None, stream or None), "GPU DEEP evaluation (device point) failed")
+
+
+def fri_phase_roots_device(d_levels: int, m_first: int, rounds: int, d_roots: int, stream: int = 0) -> None:
+    """The roots of the `rounds` trees a commit phase left back to back in d_levels (tree k: m_first >> k leaves) to d_roots, 32 bytes each."""
+    check(lib.toyni_fri_phase_roots_device(d_levels or None, m_first, rounds, d_roots or None, stream or None), "GPU phase roots failed")
+
+
 # ---- constraint programs (include/toyni_hip.h 3f) ----
 AIR_CELL, AIR_CONST, AIR_X, AIR_XINV, AIR_ADD, AIR_SUB, AIR_MUL, AIR_EMIT = range(8)
 AIR_PARAM, AIR_MAX_PARAMS = 8, 256   # include/toyni_hip.h 3p: r[dst] = params[imm], a value the program does not carry
@@ -665,6 +692,11 @@ class DeviceTranscript:
     def squeeze_ext_point(self, d_z: int, stream: int = 0) -> None:
         """The out-of-domain point (include/toyni_hip.h 3o): four challenges to d_z, squeezed again while z1 = z2 = z3 = 0."""
         check(lib.toyni_transcript_squeeze_ext_point_device(self.ptr, d_z or None, stream or None), "GPU transcript point squeeze failed")
+
+    def squeeze_point(self, d_z: int, log_N: int, shift: int, stream: int = 0) -> None:
+        """derive_z of the Fibonacci protocol (include/toyni_hip.h 3q): one challenge to d_z, squeezed again while z^N = 1 or
+        (z / shift)^N = 1, N = 2^log_N."""
+        check(lib.toyni_transcript_squeeze_point_device(self.ptr, log_N, shift, d_z or None, stream or None), "GPU transcript point squeeze failed")
 
     def absorb_fields(self, d_words: int, count: int, stream: int = 0) -> None:
         """absorb_field for `count` (<= 126) device-resident words: 8 little-endian bytes of the canonical residue each."""
