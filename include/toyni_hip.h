@@ -957,6 +957,65 @@ int toyni_fib_deep_dz_device(toyni_ntt_ctx* ctx, const uint32_t* d_trace_lde, co
 int toyni_fri_phase_roots_device(const uint8_t* d_levels, size_t m_first, unsigned rounds, uint8_t* d_roots, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * 3r. A BATCH dimension for the latency-bound tail of a proof: from "the DEEP codewords of `batch` proofs lie on the device" to "every
+ *     proof's query positions are known", and the tree-building call that also serves the trace, quotient and DEEP commitments of
+ *     `batch` proofs.  The chains of 3l are launch-bound -- a 2^12-element layer's largest launch hashes 2048 leaves on a chip of
+ *     65 536 lanes -- and proofs in flight on several streams do not overlap; here every launch of the chain works on
+ *     `batch` independent proofs instead: the same number of launches, the proof index a block coordinate of each.
+ *     THE SPECIFICATION: every call writes, for proof b < batch, exactly the bytes the single call of 3a / 3l writes when given proof
+ *     b's pointers.  The single calls are the reference; batch == 1 enqueues a chain that writes what the single call writes.
+ *     ADDRESSING: proof b's part of an array starts b * stride behind the base pointer.  Strides are size_t, in elements of the
+ *     pointed-to type (u32 words for uint32_t*, bytes for uint8_t*); a stride may exceed the proof's extent (guard bands between the
+ *     proofs stay untouched); all offset arithmetic is 64-bit.  The transcripts are an array toyni_transcript d_tr[batch], 1 KiB apart.
+ *     `status` is sticky PER PROOF: a transcript whose status is set behaves as in 3l and its neighbours do not notice.
+ *     x0, m0, final_size and the context are shared: all proofs of a batch live on the same domain.
+ *     Conventions of 3l / 3o / 3q: asynchronous on `stream`, packed-u32 words, no callback, no host read, no new environment variable;
+ *     each call is a linear chain of kernels and can be captured into a HIP graph (caveat of section 4; the phases need a context
+ *     warmed by one call on this stream with at least this batch and these sizes: the per-stream record buffer grows to `batch`
+ *     records per round).  TOYNI_FRI_TAIL_LOG and TOYNI_MERKLE_COOP_LOG keep their meaning and every setting writes the same bytes; a
+ *     tree level takes the two-wave node hash when batch x nodes <= 2^TOYNI_MERKLE_COOP_LOG, since that product is what fills the chip.
+ *     REFUSALS, on the host before anything is enqueued, the outputs untouched, in this order: TOYNI_E_NULL for a null pointer (the
+ *     pointers the single call allows to be null may be null); TOYNI_E_RANGE for batch == 0 or batch > 65535; then the single call's
+ *     refusals, with its codes and in its order; then TOYNI_E_RANGE for a stride smaller than the proof's extent or one that breaks
+ *     the single call's alignment rule for that pointer (a multiple of 16 bytes where the single call wants 16-byte alignment).  The
+ *     stride of a pointer that is null is not looked at.  What the single call accepts as "nothing to do" enqueues nothing here.
+ *     No existing entry point, kernel symbol, record layout or written byte changes.
+ *     OUT OF SCOPE: the four-to-one phase of 3m, grinding (3n), and the first half of a proof (mask, quotient, out-of-domain values,
+ *     DEEP) -- so there is no batched prover yet, and no caller inside this library is switched to these calls.
+ * ---------------------------------------------------------------------------------------------- */
+/* `batch` trees of toyni_merkle_commit_device over n leaves each (any n >= 1; n == 0 writes nothing).  Extents: value_stride >= n words;
+ * salt_stride >= 16 n bytes and a multiple of 16 (d_salts may be NULL: unsalted); level_stride in BYTES, a multiple of 16 and at least
+ * toyni_merkle_total_digests(n) * 32. */
+int toyni_merkle_commit_batch_device(const uint32_t* d_values, size_t value_stride, const uint8_t* d_salts, size_t salt_stride, size_t n,
+                                     size_t batch, uint8_t* d_levels, size_t level_stride, void* stream);
+/* Transcript b absorbs the `len` bytes at d_bytes + b * byte_stride (byte_stride >= len): one launch, one wave per transcript.  For the
+ * roots of trees built by the call above, d_bytes = the root of tree 0 and byte_stride = level_stride. */
+int toyni_transcript_absorb_batch_device(toyni_transcript* d_tr, size_t batch, const uint8_t* d_bytes, size_t byte_stride, size_t len,
+                                         void* stream);
+/* The commit phases of 3l for `batch` proofs: the arguments of the single calls, `batch` behind d_tr and a stride behind each of
+ * d_layer0, d_salts, d_layers, d_levels and d_betas.  Extents (W = 1, or 4 for the Ext call; rounds = log2(m0 / final_size)):
+ *   layer0_stride >= W m0 words; layers_stride >= W (m0 - final_size) words; both multiples of 4 for the Ext call
+ *   salt_stride   >= 16 (m0 - 2 final_size) bytes, a multiple of 16 (d_salts not NULL)
+ *   level_stride  >= 32 x the digests of all trees of a proof, in bytes, a multiple of 16
+ *   beta_stride   >= W rounds words (d_betas not NULL)
+ * beta of proof b reaches its fold through record b of the round's `batch` records in the per-stream buffer. */
+int toyni_fri_commit_phase_transcript_batch_device(toyni_ntt_ctx* ctx, const uint32_t* d_layer0, size_t layer0_stride, size_t m0, uint32_t x0,
+                                                   size_t final_size, const uint8_t* d_salts, size_t salt_stride, toyni_transcript* d_tr,
+                                                   size_t batch, uint32_t* d_layers, size_t layers_stride, uint8_t* d_levels, size_t level_stride,
+                                                   uint32_t* d_betas, size_t beta_stride, void* stream);
+int toyni_fri_commit_phase_transcript_ext_batch_device(toyni_ntt_ctx* ctx, const uint32_t* d_layer0, size_t layer0_stride, size_t m0, uint32_t x0,
+                                                       size_t final_size, const uint8_t* d_salts, size_t salt_stride, toyni_transcript* d_tr,
+                                                       size_t batch, uint32_t* d_layers, size_t layers_stride, uint8_t* d_levels,
+                                                       size_t level_stride, uint32_t* d_betas, size_t beta_stride, void* stream);
+/* toyni_transcript_squeeze_indices_device on every transcript: proof b's `count` indices at d_out + b * out_stride (out_stride >= count). */
+int toyni_transcript_squeeze_indices_batch_device(toyni_transcript* d_tr, size_t batch, size_t count, uint32_t max, uint32_t* d_out,
+                                                  size_t out_stride, void* stream);
+/* toyni_fri_query_positions_device for every proof: index_stride >= count, out_stride >= rounds x 2 count words.  The openings need
+ * nothing new: toyni_merkle_open_groups_device takes the groups of any number of trees in one launch. */
+int toyni_fri_query_positions_batch_device(const uint32_t* d_indices, size_t index_stride, size_t count, size_t m0, size_t final_size,
+                                           size_t batch, uint32_t* d_out, size_t out_stride, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:
  *     src/fibonacci.rs:133-150,186-198,222-245, src/math/polynomial.rs:134-144, src/merkle.rs:50-80).  All asynchronous on
  *     `stream`; packed u32 device data; ctx = a context of size N = the LDE size (its domain table supplies x_i = shift w_N^i).

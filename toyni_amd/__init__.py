@@ -16,6 +16,7 @@ from .domain import BabyBearDomain  # noqa: F401
 from .merkle import (MerkleTree, RowMerkleTree, ROWS_COLUMN_MAJOR, ROWS_ROW_MAJOR, merkle_commit_device,  # noqa: F401
                      merkle_commit_rows_device, merkle_open_rows_device)
 from .merkle import CosetExtMerkleTree, merkle_commit_cosets_ext_device, merkle_open_cosets_ext_device  # noqa: F401  (include/toyni_hip.h 3m)
+from .merkle import merkle_commit_batch_device  # noqa: F401  (include/toyni_hip.h 3r)
 from . import prover  # noqa: F401
 from .prover import AirBuilder, AirProgram, air_insns, air_quotient_device  # noqa: F401  (include/toyni_hip.h 3f)
 from .prover import air_ext_weights, air_quotient_ext_device  # noqa: F401  (include/toyni_hip.h 3k)

@@ -181,6 +181,15 @@ SIGNATURES = {
     "toyni_poly_eval_dz_device": (c_int, [c_void_p, c_void_p, c_size, c_void_p, c_void_p, ctypes.c_uint, c_void_p, c_void_p]),
     "toyni_fib_deep_dz_device": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_uint, c_u32, c_void_p, c_void_p, c_u32, c_void_p, c_void_p]),
     "toyni_fri_phase_roots_device": (c_int, [c_void_p, c_size, ctypes.c_uint, c_void_p, c_void_p]),
+    # section 3r
+    "toyni_merkle_commit_batch_device": (c_int, [c_void_p, c_size, c_void_p, c_size, c_size, c_size, c_void_p, c_size, c_void_p]),
+    "toyni_transcript_absorb_batch_device": (c_int, [c_void_p, c_size, c_void_p, c_size, c_size, c_void_p]),
+    "toyni_fri_commit_phase_transcript_batch_device": (c_int, [c_void_p, c_void_p, c_size, c_size, c_u32, c_size, c_void_p, c_size, c_void_p, c_size,
+                                                               c_void_p, c_size, c_void_p, c_size, c_void_p, c_size, c_void_p]),
+    "toyni_fri_commit_phase_transcript_ext_batch_device": (c_int, [c_void_p, c_void_p, c_size, c_size, c_u32, c_size, c_void_p, c_size, c_void_p, c_size,
+                                                                   c_void_p, c_size, c_void_p, c_size, c_void_p, c_size, c_void_p]),
+    "toyni_transcript_squeeze_indices_batch_device": (c_int, [c_void_p, c_size, c_size, c_u32, c_void_p, c_size, c_void_p]),
+    "toyni_fri_query_positions_batch_device": (c_int, [c_void_p, c_size, c_size, c_size, c_size, c_size, c_void_p, c_size, c_void_p]),
     # section 3c
     "toyni_fri_fold_commit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -2246,6 +2246,312 @@ __global__ void __launch_bounds__(MERKLE_TAIL_T) fri_tail_rounds_kernel(const Fr
     if (tid == 0) { a.tr->len = tr.len; a.tr->status = tr.status; }
 }
 
+// ---- a batch dimension for the latency-bound tail (include/toyni_hip.h 3r) ----
+// Batch twins of the kernels above: the same launches, each working on `batch` independent proofs that lie a stride apart.  Proof b
+// writes exactly what the single kernel writes when given proof b's pointers.  The proof index is a BLOCK coordinate: blockIdx.x where
+// one block is one proof (the one-wave and the one-workgroup kernels), blockIdx.y for the sweeps, whose blockIdx.x / gridDim.x keep
+// their meaning.  The twins are written out instead of sharing bodies with the originals, so that the originals' code -- registers,
+// LDS, occupancy -- cannot move.  Every offset is 64-bit.
+__global__ void __launch_bounds__(256) merkle_leaf_batch_kernel(const uint32_t* __restrict__ values0, size_t value_stride, const uint8_t* __restrict__ salts0,
+                                                                 size_t salt_stride, uint8_t* __restrict__ levels0, size_t level_stride, size_t n) {
+    const size_t b = blockIdx.y;   // the proof: a block coordinate, the same in every lane of every wave of the workgroup
+    const uint32_t* values = values0 + b * value_stride;
+    const uint4* salts = salts0 ? reinterpret_cast<const uint4*>(salts0 + b * salt_stride) : nullptr;
+    Digest* out = reinterpret_cast<Digest*>(levels0 + b * level_stride);
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        Digest d;
+        if (salts) {
+            const uint4 s = salts[i];
+            const uint32_t sw[4] = {s.x, s.y, s.z, s.w};
+            d = merkle_leaf(values[i], sw);
+        } else {
+            d = merkle_leaf(values[i], nullptr);
+        }
+        out[i] = d;
+    }
+}
+// level `at` (a digest offset inside a proof's tree) of m digests -> the level behind it, in every proof
+__global__ void __launch_bounds__(256) merkle_level_batch_kernel(uint8_t* __restrict__ levels0, size_t level_stride, size_t at, size_t m, size_t up) {
+    const size_t b = blockIdx.y;   // the proof: a block coordinate, wave-uniform
+    const Digest* cur = reinterpret_cast<const Digest*>(levels0 + b * level_stride) + at;
+    Digest* next = reinterpret_cast<Digest*>(levels0 + b * level_stride) + at + m;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < up; i += stride) {
+        const Digest l = cur[2 * i];
+        const Digest r = (2 * i + 1 < m) ? cur[2 * i + 1] : l;  // odd level: duplicate the last node (src/merkle.rs:38-42)
+        next[i] = merkle_node(l, r);
+    }
+}
+__global__ void __launch_bounds__(128) merkle_level_coop_batch_kernel(uint8_t* __restrict__ levels0, size_t level_stride, size_t at, size_t m, size_t up) {
+    __shared__ uint32_t sched[COOP_SCHED_WORDS];
+    const size_t b = blockIdx.y;   // the proof: a block coordinate, wave-uniform -- both barriers of merkle_node_coop are reached by every wave
+    const Digest* cur = reinterpret_cast<const Digest*>(levels0 + b * level_stride) + at;
+    Digest* next = reinterpret_cast<Digest*>(levels0 + b * level_stride) + at + m;
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool helper = TOYNI_UNIFORM(threadIdx.x >> 6) != 0;
+    const size_t i0 = (size_t)blockIdx.x * 64u + lane;
+    const size_t i = i0 < up ? i0 : up - 1;
+    const Digest l = cur[2 * i];
+    const Digest r = (2 * i + 1 < m) ? cur[2 * i + 1] : l;
+    const Digest d = merkle_node_coop(l, r, sched, lane, helper, true);
+    if (!helper && i0 < up) next[i0] = d;
+}
+// one workgroup per proof: every barrier condition below is a function of m, which all proofs share
+__global__ void __launch_bounds__(MERKLE_TAIL_T) merkle_tail_batch_kernel(uint8_t* __restrict__ levels0, size_t level_stride, size_t at, uint32_t m) {
+    __shared__ Digest lvl[MERKLE_TAIL];
+    __shared__ uint32_t sched[MERKLE_TAIL_T / 128][COOP_SCHED_WORDS];
+    const size_t b = blockIdx.x;   // the proof: a block coordinate, wave-uniform
+    const Digest* cur = reinterpret_cast<const Digest*>(levels0 + b * level_stride) + at;
+    Digest* next = reinterpret_cast<Digest*>(levels0 + b * level_stride) + at + m;
+    for (uint32_t i = threadIdx.x; i < m; i += blockDim.x) lvl[i] = cur[i];
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = TOYNI_UNIFORM(threadIdx.x >> 6);
+    const uint32_t pair = wave >> 1;
+    const bool helper = (wave & 1u) != 0u;
+    while (m > 1) {
+        const uint32_t up = (m + 1) / 2;
+        const bool active = pair * 64u < up;               // wave-uniform
+        const uint32_t i0 = pair * 64u + lane;
+        const uint32_t i = i0 < up ? i0 : up - 1;
+        Digest l{}, r{};
+        if (active) {
+            l = lvl[2 * i];
+            r = (2 * i + 1 < m) ? lvl[2 * i + 1] : l;
+        }
+        const Digest d = merkle_node_coop(l, r, sched[pair], lane, helper, active);   // its first barrier: every read of the old level is done
+        if (active && !helper && i0 < up) {
+            lvl[i0] = d;
+            next[i0] = d;
+        }
+        TOYNI_LDS_BARRIER();
+        next += up;
+        m = up;
+    }
+}
+
+// one wave per transcript
+__global__ void __launch_bounds__(TRANSCRIPT_T) transcript_absorb_batch_kernel(TranscriptState* __restrict__ tr, const uint8_t* __restrict__ src,
+                                                                                size_t byte_stride, uint32_t n) {
+    const size_t b = blockIdx.x;   // the proof: a block coordinate, wave-uniform
+    transcript_absorb_wave(tr[b], src + b * byte_stride, n, threadIdx.x, TRANSCRIPT_T);
+}
+__global__ void __launch_bounds__(TRANSCRIPT_T) transcript_squeeze_indices_batch_kernel(TranscriptState* __restrict__ tr, uint32_t count, uint32_t max,
+                                                                                         uint32_t* __restrict__ out, size_t out_stride) {
+    __shared__ uint32_t seen[TRANSCRIPT_MAX_INDICES];
+    __shared__ uint32_t flag;
+    const size_t b = blockIdx.x;   // the proof: a block coordinate, wave-uniform
+    const auto any_lane = [](bool hit) {   // as in transcript_squeeze_indices_kernel: one LDS word, a wave's LDS operations in program order
+        if (threadIdx.x == 0) flag = 0u;
+        TOYNI_WAVE_ORDER();
+        if (hit) flag = 1u;
+        TOYNI_WAVE_ORDER();
+        const uint32_t some = flag;
+        TOYNI_WAVE_ORDER();
+        return some != 0u;
+    };
+    transcript_squeeze_indices(tr[b], count, max, out + b * out_stride, seen, threadIdx.x, TRANSCRIPT_T, any_lane);
+}
+__global__ void __launch_bounds__(256) fri_query_positions_batch_kernel(const uint32_t* __restrict__ indices, size_t index_stride, uint32_t count, uint64_t m0,
+                                                                        uint64_t total, uint32_t* __restrict__ out, size_t out_stride) {
+    const size_t b = blockIdx.y;   // the proof: a block coordinate, wave-uniform
+    const uint32_t* idx = indices + b * index_stride;
+    uint32_t* o = out + b * out_stride;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += stride) o[t] = fri_query_position(idx, count, m0, t);
+}
+
+// Between two rounds, one wave per proof: proof b absorbs its root, squeezes and leaves its record at rec + b * rec_stride.
+__global__ void __launch_bounds__(TRANSCRIPT_T) fri_transcript_round_batch_kernel(TranscriptState* __restrict__ tr0, const uint8_t* __restrict__ root0,
+                                                                                   size_t root_stride, uint32_t nsqueeze, uint32_t c0, uint32_t c1,
+                                                                                   uint32_t* __restrict__ rec0, uint32_t rec_stride,
+                                                                                   uint32_t* __restrict__ betas0, size_t beta_stride) {
+    __shared__ uint32_t beta[4];
+    const size_t b = blockIdx.x;   // the proof: a block coordinate, wave-uniform; the barrier below hangs on nsqueeze alone
+    TranscriptState& tr = tr0[b];
+    uint32_t* rec = rec0 + b * rec_stride;
+    uint32_t* betas = betas0 ? betas0 + b * beta_stride : nullptr;
+    if (threadIdx.x == 0) {
+        if (root0) transcript_absorb(tr, root0 + b * root_stride, 32u);
+        transcript_squeeze(tr, beta, nsqueeze);
+    }
+    if (nsqueeze == 0u) return;
+    __syncthreads();
+    if (threadIdx.x < nsqueeze) {
+        const uint32_t v = beta[threadIdx.x];
+        if (betas) betas[threadIdx.x] = v;
+        rec[threadIdx.x] = transcript_factor(v, c0);
+        if (nsqueeze == 4u) rec[4u + threadIdx.x] = transcript_factor(v, c1);
+    }
+}
+
+// The folds: proof b reads its layer at evals + b * in_stride, writes out + b * out_stride (strides in words), its leaves at
+// levels + b * level_stride (bytes), its salts at salts + b * salt_stride (bytes), with the factor of record b.
+struct FoldBatch {
+    size_t in_stride, out_stride, salt_stride, level_stride;
+    uint32_t rec_stride;
+};
+__global__ void __launch_bounds__(256) fri_fold_commit_rec_batch_kernel(const FoldArgs f0, const FoldBatch st, const uint32_t* __restrict__ rec,
+                                                                        const uint8_t* __restrict__ salts0, uint8_t* __restrict__ levels0) {
+    const size_t b = blockIdx.y;   // the proof: a block coordinate, wave-uniform
+    FoldArgs f = f0;
+    f.evals = f0.evals + b * st.in_stride;
+    f.out = f0.out + b * st.out_stride;
+    f.coef = rec[b * st.rec_stride];
+    const uint4* salts = salts0 ? reinterpret_cast<const uint4*>(salts0 + b * st.salt_stride) : nullptr;
+    Digest* leaves = reinterpret_cast<Digest*>(levels0 + b * st.level_stride);
+    const uint64_t half = f.half;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < half; i += stride) {
+        const uint32_t r = fold_one(f, i, f.evals[i], f.evals[i + half]);
+        f.out[i] = r;
+        if (salts) {
+            const uint4 sv = salts[i];
+            const uint32_t sw[4] = {sv.x, sv.y, sv.z, sv.w};
+            leaves[i] = merkle_leaf(r, sw);
+        } else {
+            leaves[i] = merkle_leaf(r, nullptr);
+        }
+    }
+}
+template <bool SALTED>
+__global__ void __launch_bounds__(256) fri_fold_ext_commit_rec_batch_kernel(const FoldArgs f, const FoldBatch st, const uint32_t* __restrict__ rec,
+                                                                            const uint8_t* __restrict__ salts0, uint8_t* __restrict__ levels0) {
+    const size_t b = blockIdx.y;   // the proof: a block coordinate, wave-uniform
+    const ExtFactor beta_half = *reinterpret_cast<const ExtFactor*>(rec + b * st.rec_stride);
+    const uint64_t half = f.half;
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    const uint4* ea = reinterpret_cast<const uint4*>(f.evals + b * st.in_stride);
+    const uint4* eb = ea + half;
+    uint4* o = reinterpret_cast<uint4*>(f.out + b * st.out_stride);
+    const uint4* salts = reinterpret_cast<const uint4*>(salts0 + (SALTED ? b * st.salt_stride : 0));
+    Digest* leaves = reinterpret_cast<Digest*>(levels0 + b * st.level_stride);
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < half; i += stride) {
+        const uint32_t scaleR = mont_mul(subdomain_mont(f.dom, (uint32_t)i), f.coef);
+        const uint4 a = ea[i], c = eb[i];
+        uint32_t sw[4] = {0u, 0u, 0u, 0u};
+        if constexpr (SALTED) {
+            const uint4 s = salts[i];
+            sw[0] = s.x; sw[1] = s.y; sw[2] = s.z; sw[3] = s.w;
+        }
+        const FoldExtLeaf r = fold_ext_commit_one<SALTED>(Ext4{{a.x, a.y, a.z, a.w}}, Ext4{{c.x, c.y, c.z, c.w}}, scaleR, beta_half, sw);
+        o[i] = make_uint4(r.folded.c[0], r.folded.c[1], r.folded.c[2], r.folded.c[3]);
+        leaves[i] = r.leaf;
+    }
+}
+
+// fri_tail_rounds_kernel, one workgroup per proof.  The proof index only moves the six pointers; m, final_size and with them every
+// loop count and every barrier condition are shared by all proofs of the launch, so each workgroup runs the original's barrier
+// sequence.  a.cur, a.out, a.levels, a.salts, a.betas and a.tr are proof 0's; a null a.salts / a.betas is null for every proof.
+struct FriTailBatch { size_t cur_stride, out_stride, level_stride, salt_stride, beta_stride; };   // words, words, bytes, bytes, words
+template <bool EXT>
+__global__ void __launch_bounds__(MERKLE_TAIL_T) fri_tail_rounds_batch_kernel(const FriTailArgs a, const FriTailBatch st) {
+    constexpr uint32_t W = EXT ? 4u : 1u, NSQ = EXT ? 4u : 1u;
+    __shared__ uint32_t layer[2 * MERKLE_TAIL * W];
+    __shared__ Digest lvl[MERKLE_TAIL];
+    __shared__ uint32_t sched[MERKLE_TAIL_T / 128][COOP_SCHED_WORDS];
+    __shared__ TranscriptState tr;
+    __shared__ uint32_t beta[4];
+    const size_t b = blockIdx.x;   // the proof: a block coordinate, the same in every wave -- the barriers below depend on m alone
+    const uint32_t* in = a.cur + b * st.cur_stride;
+    TranscriptState* gtr = a.tr + b;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    const uint32_t wave = TOYNI_UNIFORM(tid >> 6);
+    const uint32_t pair = wave >> 1;
+    const bool helper = (wave & 1u) != 0u;
+    for (uint32_t i = tid; i < a.m * W; i += blockDim.x) layer[i] = in[i];
+    for (uint32_t i = tid; i < TRANSCRIPT_CAPACITY; i += blockDim.x) tr.bytes[i] = gtr->bytes[i];
+    if (tid == 0) { tr.len = gtr->len; tr.status = gtr->status; }
+    __syncthreads();
+    uint32_t m = a.m, shift = 0, xinvR = a.xinvR;
+    uint32_t* out = a.out + b * st.out_stride;
+    Digest* levels = reinterpret_cast<Digest*>(reinterpret_cast<uint8_t*>(a.levels) + b * st.level_stride);
+    const uint4* salts = a.salts ? reinterpret_cast<const uint4*>(reinterpret_cast<const uint8_t*>(a.salts) + b * st.salt_stride) : nullptr;
+    uint32_t* betas = a.betas ? a.betas + b * st.beta_stride : nullptr;
+    bool have_root = false;
+    while (m > a.final_size) {
+        const uint32_t half = m >> 1;
+        const bool salted = salts && half != a.final_size;
+        if (tid == 0u) {
+            if (have_root) transcript_absorb(tr, reinterpret_cast<const uint8_t*>(&lvl[0]), 32u);
+            transcript_squeeze(tr, beta, NSQ);
+            if (betas) {
+#pragma unroll
+                for (uint32_t k = 0; k < NSQ; ++k) betas[k] = beta[k];
+            }
+        }
+        __syncthreads();   // beta is there; the root has been read before a leaf of this round replaces it
+        if (tid < half) {
+            uint32_t sw[4] = {0u, 0u, 0u, 0u};
+            if (salted) {
+                const uint4 sv = salts[tid];
+                sw[0] = sv.x; sw[1] = sv.y; sw[2] = sv.z; sw[3] = sv.w;
+            }
+            Digest d;
+            if constexpr (EXT) {
+                ExtFactor f;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) { f.b[k] = transcript_factor(beta[k], a.half_r2); f.b11[k] = transcript_factor(beta[k], a.half11_r2); }
+                const uint32_t scaleR = mont_mul(subdomain_mont(a.dom, tid << shift), xinvR);
+                const uint32_t* pa = layer + 4u * tid;
+                const uint32_t* pb = layer + 4u * (tid + half);
+                const Ext4 va{{pa[0], pa[1], pa[2], pa[3]}}, vb{{pb[0], pb[1], pb[2], pb[3]}};
+                const FoldExtLeaf r = salted ? fold_ext_commit_one<true>(va, vb, scaleR, f, sw) : fold_ext_commit_one<false>(va, vb, scaleR, f, sw);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) layer[4u * tid + (uint32_t)k] = r.folded.c[k];
+                reinterpret_cast<uint4*>(out)[tid] = make_uint4(r.folded.c[0], r.folded.c[1], r.folded.c[2], r.folded.c[3]);
+                d = r.leaf;
+            } else {
+                FoldArgs f{};
+                f.dom = a.dom;
+                f.coef = mont_mul(transcript_factor(beta[0], a.half_r2), xinvR);   // Montgomery form of beta / (2 x)
+                const uint32_t r = fold_one(f, (uint64_t)(tid << shift), layer[tid], layer[tid + half]);
+                layer[tid] = r;
+                out[tid] = r;
+                if (salted) d = merkle_leaf(r, sw);
+                else d = merkle_leaf(r, nullptr);
+            }
+            lvl[tid] = d;
+            levels[tid] = d;
+        }
+        __syncthreads();   // the leaves, and the folded layer, before anything reads them
+        uint32_t n = half;
+        Digest* next = levels + half;
+        while (n > 1u) {
+            const uint32_t up = (n + 1u) / 2u;
+            const bool active = pair * 64u < up;               // wave-uniform
+            const uint32_t i0 = pair * 64u + lane;
+            const uint32_t i = i0 < up ? i0 : up - 1u;
+            Digest l{}, r{};
+            if (active) {
+                l = lvl[2u * i];
+                r = (2u * i + 1u < n) ? lvl[2u * i + 1u] : l;
+            }
+            const Digest d = merkle_node_coop(l, r, sched[pair], lane, helper, active);   // its first barrier: every read of the old level is done
+            if (active && !helper && i0 < up) {
+                lvl[i0] = d;
+                next[i0] = d;
+            }
+            TOYNI_LDS_BARRIER();
+            next += up;
+            n = up;
+        }
+        levels += 2u * half - 1u;
+        out += half * W;
+        if (salted) salts += half;
+        if (betas) betas += NSQ;
+        xinvR = mont_mul(xinvR, xinvR);   // the squared domain of the next layer
+        ++shift;
+        m = half;
+        have_root = true;
+    }
+    if (tid == 0u && have_root) transcript_absorb(tr, reinterpret_cast<const uint8_t*>(&lvl[0]), 32u);
+    __syncthreads();
+    for (uint32_t i = tid; i < TRANSCRIPT_CAPACITY; i += blockDim.x) gtr->bytes[i] = tr.bytes[i];
+    if (tid == 0) { gtr->len = tr.len; gtr->status = tr.status; }
+}
+
 #ifndef TOYNI_KERNEL_TEXT_ONLY
 // ------------------------------------------------------------------------------------------------
 // context
@@ -4183,6 +4489,216 @@ int toyni_fri_commit_phase_transcript_ext_device(toyni_ntt_ctx* c, const uint32_
     if (m0 > c->n) return TOYNI_E_INVALID_SIZE;
     if (m0 <= final_size) return TOYNI_OK;
     return commit_phase_transcript(c, d_layer0, m0, x0, final_size, 4, d_salts, d_tr, d_layers, d_levels, d_betas, (hipStream_t)stream);
+}
+
+// ---- the batch dimension of the tail (include/toyni_hip.h 3r) ----
+// Order of the refusals in every call: null pointers, batch, the single call's own in the single call's order, the strides.
+constexpr size_t BATCH_MAX = 65535;   // the proof index is a block coordinate: gridDim.y
+static bool batch_ok(size_t batch) { return batch >= 1 && batch <= BATCH_MAX; }
+
+// The levels above the leaf hashes in every proof's tree; the tree starts `at` digests into the proof's region.  A level takes the
+// two-wave node hash when batch x nodes -- what the launch spreads over the chip -- is at most 2^TOYNI_MERKLE_COOP_LOG.
+static int enqueue_merkle_upper_batch(uint8_t* d_levels, size_t level_stride, size_t at, size_t n, size_t batch, hipStream_t s) {
+    static const int coop_log = env_int("TOYNI_MERKLE_COOP_LOG", 14);
+    size_t m = n;
+    const unsigned by = (unsigned)batch;
+    while (m > MERKLE_TAIL) {
+        const size_t up = (m + 1) / 2;
+        if (coop_log >= 0 && up * batch <= ((size_t)1 << coop_log))
+            hipLaunchKernelGGL(merkle_level_coop_batch_kernel, dim3((unsigned)((up + 63) / 64), by), dim3(128), 0, s, d_levels, level_stride, at, m, up);
+        else
+            hipLaunchKernelGGL(merkle_level_batch_kernel, dim3(grid_for(up), by), dim3(256), 0, s, d_levels, level_stride, at, m, up);
+        at += m;
+        m = up;
+    }
+    if (m > 1) hipLaunchKernelGGL(merkle_tail_batch_kernel, dim3(by), dim3(MERKLE_TAIL_T), 0, s, d_levels, level_stride, at, (uint32_t)m);
+    return (int)hipGetLastError();
+}
+
+int toyni_merkle_commit_batch_device(const uint32_t* d_values, size_t value_stride, const uint8_t* d_salts, size_t salt_stride, size_t n, size_t batch,
+                                     uint8_t* d_levels, size_t level_stride, void* stream) {
+    if (!d_values || !d_levels) return TOYNI_E_NULL;
+    if (!batch_ok(batch)) return TOYNI_E_RANGE;
+    if (n == 0) return TOYNI_OK;
+    if (((uintptr_t)d_levels & 15) || ((uintptr_t)d_salts & 15)) return TOYNI_E_RANGE;  // 16-byte accesses
+    if (value_stride < n || (d_salts && (salt_stride < n * 16 || (salt_stride & 15)))) return TOYNI_E_RANGE;
+    if (level_stride < toyni_merkle_total_digests(n) * 32 || (level_stride & 15)) return TOYNI_E_RANGE;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(merkle_leaf_batch_kernel, dim3(grid_for(n), (unsigned)batch), dim3(256), 0, s, d_values, value_stride, d_salts, salt_stride, d_levels,
+                       level_stride, n);
+    return enqueue_merkle_upper_batch(d_levels, level_stride, 0, n, batch, s);
+}
+
+int toyni_transcript_absorb_batch_device(toyni_transcript* d_tr, size_t batch, const uint8_t* d_bytes, size_t byte_stride, size_t len, void* stream) {
+    if (!d_tr || (!d_bytes && len)) return TOYNI_E_NULL;
+    if (!batch_ok(batch)) return TOYNI_E_RANGE;
+    if (((uintptr_t)d_tr & 15) || len > TOYNI_TRANSCRIPT_CAPACITY) return TOYNI_E_RANGE;
+    if (byte_stride < len) return TOYNI_E_RANGE;
+    if (len == 0) return TOYNI_OK;
+    hipLaunchKernelGGL(transcript_absorb_batch_kernel, dim3((unsigned)batch), dim3(TRANSCRIPT_T), 0, (hipStream_t)stream, transcript_of(d_tr), d_bytes,
+                       byte_stride, (uint32_t)len);
+    return (int)hipGetLastError();
+}
+
+int toyni_transcript_squeeze_indices_batch_device(toyni_transcript* d_tr, size_t batch, size_t count, uint32_t max, uint32_t* d_out, size_t out_stride,
+                                                  void* stream) {
+    if (!d_tr || !d_out) return TOYNI_E_NULL;
+    if (!batch_ok(batch)) return TOYNI_E_RANGE;
+    if (((uintptr_t)d_tr & 15) || ((uintptr_t)d_out & 3)) return TOYNI_E_RANGE;
+    if (count == 0 || count > TRANSCRIPT_MAX_INDICES || max == 0 || count > max) return TOYNI_E_RANGE;
+    if (out_stride < count) return TOYNI_E_RANGE;
+    hipLaunchKernelGGL(transcript_squeeze_indices_batch_kernel, dim3((unsigned)batch), dim3(TRANSCRIPT_T), 0, (hipStream_t)stream, transcript_of(d_tr),
+                       (uint32_t)count, max, d_out, out_stride);
+    return (int)hipGetLastError();
+}
+
+int toyni_fri_query_positions_batch_device(const uint32_t* d_indices, size_t index_stride, size_t count, size_t m0, size_t final_size, size_t batch,
+                                           uint32_t* d_out, size_t out_stride, void* stream) {
+    if (!d_indices || !d_out) return TOYNI_E_NULL;
+    if (!batch_ok(batch)) return TOYNI_E_RANGE;
+    if (((uintptr_t)d_indices & 3) || ((uintptr_t)d_out & 3)) return TOYNI_E_RANGE;
+    if (!is_pow2(m0) || !is_pow2(final_size) || final_size < 1 || (uint64_t)m0 > ((uint64_t)1 << 32) || count > 65536) return TOYNI_E_RANGE;
+    const uint64_t total = m0 > final_size ? (uint64_t)(ilog2(m0) - ilog2(final_size)) * 2u * count : 0;
+    if (index_stride < count || out_stride < total) return TOYNI_E_RANGE;
+    if (total == 0) return TOYNI_OK;
+    hipLaunchKernelGGL(fri_query_positions_batch_kernel, dim3(grid_for(total), (unsigned)batch), dim3(256), 0, (hipStream_t)stream, d_indices, index_stride,
+                       (uint32_t)count, (uint64_t)m0, total, d_out, out_stride);
+    return (int)hipGetLastError();
+}
+
+// The strides of a batched phase (include/toyni_hip.h 3r): words, bytes, words, bytes, words.
+struct PhaseStrides { size_t layer0, salts, layers, levels, betas; };
+// a proof's extents under the sizes the entry point has accepted (m0 >= final_size, both powers of two)
+static bool phase_strides_ok(const PhaseStrides& st, size_t m0, size_t final_size, size_t words, bool salted, bool betas) {
+    const size_t rounds = m0 > final_size ? (size_t)(ilog2(m0) - ilog2(final_size)) : 0;
+    size_t digests = 0;
+    for (size_t m = m0; m > final_size; m >>= 1) digests += toyni_merkle_total_digests(m >> 1);
+    const size_t folded = m0 > final_size ? m0 - final_size : 0;                      // m0 / 2 + ... + final_size elements
+    const size_t salted_leaves = folded > final_size ? folded - final_size : 0;       // every folded layer but the final one
+    if (st.layer0 < m0 * words || st.layers < folded * words || st.levels < digests * 32 || (st.levels & 15)) return false;
+    if (words == 4 && ((st.layer0 | st.layers) & 3)) return false;                    // the Ext call's 16-byte layers
+    if (salted && (st.salts < salted_leaves * 16 || (st.salts & 15))) return false;
+    if (betas && st.betas < rounds * words) return false;
+    return true;
+}
+
+// commit_phase_transcript with `batch` proofs per launch: the same chain, round k reading records k * batch .. k * batch + batch - 1.
+static int commit_phase_transcript_batch(toyni_ntt_ctx* c, const uint32_t* d_layer0, size_t m0, uint32_t x0, size_t final_size, size_t words,
+                                         const uint8_t* d_salts, toyni_transcript* d_tr, size_t batch, uint32_t* d_layers, uint8_t* d_levels,
+                                         uint32_t* d_betas, const PhaseStrides& st, hipStream_t s) {
+    const bool ext = words == 4;
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    const size_t rounds = (size_t)(ilog2(m0) - ilog2(final_size));
+    if (int rc = grow(c, s, (void**)&sc.d_fri_rec, &sc.fri_rec_words, std::max(FRI_REC_WORDS, (rounds + 1) * batch * FRI_REC_STRIDE), sizeof(uint32_t)))
+        return rc;
+    TranscriptState* tr = transcript_of(d_tr);
+    const unsigned by = (unsigned)batch;
+    const uint32_t nsq = ext ? 4u : 1u;
+    const uint32_t half_r2 = to_mont_host(to_mont_host(BB_HALF)), half11_r2 = to_mont_host(to_mont_host(bb_mul_host(BB_HALF, 11u)));
+    const auto base_r2 = [](uint32_t x) { return to_mont_host(to_mont_host(bb_mul_host(BB_HALF, bb_inv_host(x)))); };
+    // proof 0's pointers; `in_stride` is layer 0's stride in the first round and the folded layers' afterwards
+    const uint32_t* cur = d_layer0;
+    size_t in_stride = st.layer0;
+    uint32_t* out = d_layers;
+    size_t level_at = 0;               // digests into a proof's d_levels
+    const uint8_t* salts = d_salts;
+    uint32_t* betas = d_betas;
+    uint32_t x = x0;
+    uint32_t* rec = sc.d_fri_rec;
+    static const int tail_log = std::min(env_int("TOYNI_FRI_TAIL_LOG", 9), ilog2(MERKLE_TAIL));
+    const size_t tail_leaves = tail_log < 0 ? 0 : (size_t)1 << tail_log;
+    size_t m = m0;
+    if ((m >> 1) > tail_leaves)
+        hipLaunchKernelGGL(fri_transcript_round_batch_kernel, dim3(by), dim3(TRANSCRIPT_T), 0, s, tr, static_cast<const uint8_t*>(nullptr), (size_t)0, nsq,
+                           ext ? half_r2 : base_r2(x), half11_r2, rec, (uint32_t)FRI_REC_STRIDE, betas, st.betas);
+    for (; m > final_size && (m >> 1) > tail_leaves; m >>= 1) {
+        const size_t half = m >> 1;
+        const bool last = half == final_size;
+        const size_t digests = toyni_merkle_total_digests(half);
+        const uint8_t* round_salts = last ? nullptr : salts;
+        uint8_t* leaves = d_levels + level_at * 32;
+        FoldArgs f{};
+        f.evals = cur;
+        f.out = out;
+        f.dom = sub_domain(c->plan, c->d_inv, c->plan.log_n - ilog2(m));
+        f.half = half;
+        const FoldBatch fb{in_stride, st.layers, st.salts, st.levels, (uint32_t)FRI_REC_STRIDE};
+        const dim3 grid(grid_for(half), by), block(256);
+        if (ext) {
+            f.coef = to_mont_host(bb_inv_host(x));
+            if (round_salts) hipLaunchKernelGGL((fri_fold_ext_commit_rec_batch_kernel<true>), grid, block, 0, s, f, fb, (const uint32_t*)rec, round_salts, leaves);
+            else hipLaunchKernelGGL((fri_fold_ext_commit_rec_batch_kernel<false>), grid, block, 0, s, f, fb, (const uint32_t*)rec, round_salts, leaves);
+        } else {
+            hipLaunchKernelGGL(fri_fold_commit_rec_batch_kernel, grid, block, 0, s, f, fb, (const uint32_t*)rec, round_salts, leaves);
+        }
+        if (int rc = enqueue_merkle_upper_batch(d_levels, st.levels, level_at, half, batch, s)) return rc;
+        const uint8_t* root = d_levels + (level_at + digests - 1) * 32;
+        cur = out;
+        in_stride = st.layers;
+        out += half * words;
+        level_at += digests;
+        if (salts && !last) salts += half * 16;
+        if (betas) betas += nsq;
+        x = bb_mul_host(x, x);
+        rec += batch * FRI_REC_STRIDE;
+        const bool tail_next = (half >> 1) <= tail_leaves;
+        hipLaunchKernelGGL(fri_transcript_round_batch_kernel, dim3(by), dim3(TRANSCRIPT_T), 0, s, tr, root, st.levels, last || tail_next ? 0u : nsq,
+                           ext ? half_r2 : base_r2(x), half11_r2, rec, (uint32_t)FRI_REC_STRIDE, betas, st.betas);
+    }
+    if (m > final_size) {
+        FriTailArgs a{};
+        a.cur = cur;
+        a.out = out;
+        a.levels = reinterpret_cast<Digest*>(d_levels + level_at * 32);
+        a.salts = reinterpret_cast<const uint4*>(salts);
+        a.tr = tr;
+        a.betas = betas;
+        a.dom = sub_domain(c->plan, c->d_inv, c->plan.log_n - ilog2(m));
+        a.m = (uint32_t)m;
+        a.final_size = (uint32_t)final_size;
+        a.xinvR = to_mont_host(bb_inv_host(x));
+        a.half_r2 = half_r2;
+        a.half11_r2 = half11_r2;
+        const FriTailBatch tb{in_stride, st.layers, st.levels, st.salts, st.betas};
+        if (ext) hipLaunchKernelGGL((fri_tail_rounds_batch_kernel<true>), dim3(by), dim3(MERKLE_TAIL_T), 0, s, a, tb);
+        else hipLaunchKernelGGL((fri_tail_rounds_batch_kernel<false>), dim3(by), dim3(MERKLE_TAIL_T), 0, s, a, tb);
+    }
+    return (int)hipGetLastError();
+}
+
+int toyni_fri_commit_phase_transcript_batch_device(toyni_ntt_ctx* c, const uint32_t* d_layer0, size_t layer0_stride, size_t m0, uint32_t x0,
+                                                   size_t final_size, const uint8_t* d_salts, size_t salt_stride, toyni_transcript* d_tr, size_t batch,
+                                                   uint32_t* d_layers, size_t layers_stride, uint8_t* d_levels, size_t level_stride, uint32_t* d_betas,
+                                                   size_t beta_stride, void* stream) {
+    if (!c || !d_layer0 || !d_tr || !d_layers || !d_levels) return TOYNI_E_NULL;
+    if (!batch_ok(batch)) return TOYNI_E_RANGE;
+    if (!is_pow2(m0) || !is_pow2(final_size) || final_size < 1 || m0 > c->n) return TOYNI_E_INVALID_SIZE;
+    if (x0 == 0 || x0 >= BB_P) return TOYNI_E_RANGE;
+    if (((uintptr_t)d_levels & 15) || ((uintptr_t)d_salts & 15) || ((uintptr_t)d_tr & 15) || ((uintptr_t)d_betas & 3)) return TOYNI_E_RANGE;
+    const PhaseStrides st{layer0_stride, salt_stride, layers_stride, level_stride, beta_stride};
+    if (!phase_strides_ok(st, m0, final_size, 1, d_salts != nullptr, d_betas != nullptr)) return TOYNI_E_RANGE;
+    if (m0 <= final_size) return TOYNI_OK;
+    return commit_phase_transcript_batch(c, d_layer0, m0, x0, final_size, 1, d_salts, d_tr, batch, d_layers, d_levels, d_betas, st, (hipStream_t)stream);
+}
+
+int toyni_fri_commit_phase_transcript_ext_batch_device(toyni_ntt_ctx* c, const uint32_t* d_layer0, size_t layer0_stride, size_t m0, uint32_t x0,
+                                                       size_t final_size, const uint8_t* d_salts, size_t salt_stride, toyni_transcript* d_tr, size_t batch,
+                                                       uint32_t* d_layers, size_t layers_stride, uint8_t* d_levels, size_t level_stride,
+                                                       uint32_t* d_betas, size_t beta_stride, void* stream) {
+    if (!c || !d_layer0 || !d_tr || !d_layers || !d_levels) return TOYNI_E_NULL;
+    if (!batch_ok(batch)) return TOYNI_E_RANGE;
+    if (!is_pow2(m0) || !is_pow2(final_size) || final_size < 1) return TOYNI_E_INVALID_SIZE;
+    if (x0 == 0) return TOYNI_E_ZERO_INVERSE;
+    if (x0 >= BB_P) return TOYNI_E_RANGE;
+    if ((((uintptr_t)d_layer0 | (uintptr_t)d_layers | (uintptr_t)d_levels | (uintptr_t)d_salts | (uintptr_t)d_tr) & 15) || ((uintptr_t)d_betas & 3))
+        return TOYNI_E_RANGE;
+    if (m0 > c->n) return TOYNI_E_INVALID_SIZE;
+    const PhaseStrides st{layer0_stride, salt_stride, layers_stride, level_stride, beta_stride};
+    if (!phase_strides_ok(st, m0, final_size, 4, d_salts != nullptr, d_betas != nullptr)) return TOYNI_E_RANGE;
+    if (m0 <= final_size) return TOYNI_OK;
+    return commit_phase_transcript_batch(c, d_layer0, m0, x0, final_size, 4, d_salts, d_tr, batch, d_layers, d_levels, d_betas, st, (hipStream_t)stream);
 }
 
 // ---- four-to-one Ext FRI rounds under coset leaves (include/toyni_hip.h 3m) ----

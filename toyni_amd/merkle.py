@@ -62,6 +62,14 @@ def merkle_commit_device(d_values: int, d_salts: int, n: int, d_levels: int, str
     check(lib.toyni_merkle_commit_device(d_values, d_salts or None, n, d_levels, stream or None), "GPU Merkle commit failed")
 
 
+def merkle_commit_batch_device(d_values: int, value_stride: int, d_salts: int, salt_stride: int, n: int, batch: int, d_levels: int,
+                               level_stride: int, stream: int = 0) -> None:
+    """`batch` trees of merkle_commit_device in one chain of launches (include/toyni_hip.h 3r): tree b's arrays lie b strides behind the
+    base pointers; value_stride in words, salt_stride and level_stride in bytes."""
+    check(lib.toyni_merkle_commit_batch_device(d_values, value_stride, d_salts or None, salt_stride, n, batch, d_levels, level_stride,
+                                               stream or None), "GPU batched Merkle commit failed")
+
+
 ROWS_COLUMN_MAJOR = 0   # TOYNI_ROWS_COLUMN_MAJOR: element (i, c) at values[c * col_stride + i]
 ROWS_ROW_MAJOR = 1      # TOYNI_ROWS_ROW_MAJOR:    element (i, c) at values[i * width + c]
 

@@ -756,6 +756,103 @@ def fri_commit_phase_transcript_ext_device(ctx, d_layer0: int, m0: int, x0: int,
           "GPU Ext FRI commit phase (device transcript) failed")
 
 
+# ---- a batch dimension for the tail of a proof (include/toyni_hip.h 3r) ----
+class DeviceTranscriptBatch:
+    """toyni_transcript d_tr[batch]: one DeviceTranscript per proof in one allocation, 1 KiB apart, every operation one launch for
+    all of them.  `status` is sticky per proof.  Every method but `download` and `status` only enqueues on `stream`."""
+
+    def __init__(self, batch: int):
+        if batch < 1:
+            raise ValueError("a transcript batch holds at least one transcript")
+        p = ctypes.c_void_p()
+        check(lib.toyni_malloc(ctypes.byref(p), 1024 * batch), "device allocation of a transcript batch failed")
+        self.ptr, self.batch = p.value, batch
+        self._staged = []    # host copies that an enqueued upload may still read
+
+    @classmethod
+    def from_states(cls, states, stream: int = 0) -> "DeviceTranscriptBatch":
+        """One state per proof; the lengths may differ."""
+        tr = cls(len(states))
+        tr.load(states, stream)
+        return tr
+
+    def load(self, states, stream: int = 0) -> None:
+        if len(states) != self.batch:
+            raise ValueError(f"{self.batch} states are needed")
+        host = np.zeros((self.batch, 1024), dtype=np.uint8)
+        for b, state in enumerate(states):
+            if len(state) > TRANSCRIPT_CAPACITY:
+                raise ValueError(f"a device transcript holds at most {TRANSCRIPT_CAPACITY} bytes")
+            host[b, :4] = np.frombuffer(np.uint32(len(state)).tobytes(), dtype=np.uint8)
+            host[b, 16:16 + len(state)] = np.frombuffer(bytes(state), dtype=np.uint8)
+        self._staged = self._staged[-7:] + [host]
+        check(lib.toyni_memcpy_h2d_async(self.ptr, host.ctypes.data, host.nbytes, stream or None), "upload of a transcript batch failed")
+
+    def absorb_device(self, d_bytes: int, byte_stride: int, length: int, stream: int = 0) -> None:
+        """Transcript b absorbs `length` bytes at d_bytes + b * byte_stride."""
+        check(lib.toyni_transcript_absorb_batch_device(self.ptr, self.batch, d_bytes or None, byte_stride, length, stream or None),
+              "GPU batched transcript absorb failed")
+
+    def squeeze_indices(self, d_out: int, out_stride: int, count: int, mx: int, stream: int = 0) -> None:
+        """Per proof `count` distinct values below `mx` to d_out + b * out_stride words."""
+        check(lib.toyni_transcript_squeeze_indices_batch_device(self.ptr, self.batch, count, mx, d_out, out_stride, stream or None),
+              "GPU batched transcript index squeeze failed")
+
+    def download(self):
+        """[(state bytes, status)] per proof after a synchronous copy (synchronise the stream that carries the work first)."""
+        host = np.zeros((self.batch, 1024), dtype=np.uint8)
+        check(lib.toyni_memcpy_d2h(host.ctypes.data, self.ptr, host.nbytes), "download of a transcript batch failed")
+        out = []
+        for b in range(self.batch):
+            length, status = (int(v) for v in host[b, :8].view(np.uint32))
+            out.append((host[b, 16:16 + min(length, TRANSCRIPT_CAPACITY)].tobytes(), status))
+        return out
+
+    def status(self):
+        return [s for _, s in self.download()]
+
+    def free(self) -> None:
+        if self.ptr:
+            lib.toyni_free(self.ptr)
+            self.ptr = 0
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:  # noqa: BLE001  (interpreter shutdown)
+            pass
+
+
+def fri_query_positions_batch_device(d_indices: int, index_stride: int, count: int, m0: int, final_size: int, batch: int, d_out: int,
+                                     out_stride: int, stream: int = 0) -> None:
+    check(lib.toyni_fri_query_positions_batch_device(d_indices, index_stride, count, m0, final_size, batch, d_out, out_stride, stream or None),
+          "GPU batched query positions failed")
+
+
+def _phase_batch(entry, what, ctx, d_layer0, layer0_stride, m0, x0, final_size, d_salts, salt_stride, transcripts, d_layers, layers_stride,
+                 d_levels, level_stride, d_betas, beta_stride, stream):
+    check(entry(ctx.handle, d_layer0, layer0_stride, m0, x0, final_size, d_salts or None, salt_stride, transcripts.ptr, transcripts.batch,
+                d_layers, layers_stride, d_levels, level_stride, d_betas or None, beta_stride, stream or None), what)
+
+
+def fri_commit_phase_transcript_batch_device(ctx, d_layer0: int, layer0_stride: int, m0: int, x0: int, final_size: int, d_salts: int,
+                                             salt_stride: int, transcripts: DeviceTranscriptBatch, d_layers: int, layers_stride: int,
+                                             d_levels: int, level_stride: int, d_betas: int = 0, beta_stride: int = 0, stream: int = 0) -> None:
+    """fri_commit_phase_transcript_device for transcripts.batch proofs in one chain of launches; strides in words, bytes for the salts
+    and the levels."""
+    _phase_batch(lib.toyni_fri_commit_phase_transcript_batch_device, "GPU batched FRI commit phase failed", ctx, d_layer0, layer0_stride, m0, x0,
+                 final_size, d_salts, salt_stride, transcripts, d_layers, layers_stride, d_levels, level_stride, d_betas, beta_stride, stream)
+
+
+def fri_commit_phase_transcript_ext_batch_device(ctx, d_layer0: int, layer0_stride: int, m0: int, x0: int, final_size: int, d_salts: int,
+                                                 salt_stride: int, transcripts: DeviceTranscriptBatch, d_layers: int, layers_stride: int,
+                                                 d_levels: int, level_stride: int, d_betas: int = 0, beta_stride: int = 0,
+                                                 stream: int = 0) -> None:
+    """The same over Ext-valued layers."""
+    _phase_batch(lib.toyni_fri_commit_phase_transcript_ext_batch_device, "GPU batched Ext FRI commit phase failed", ctx, d_layer0, layer0_stride,
+                 m0, x0, final_size, d_salts, salt_stride, transcripts, d_layers, layers_stride, d_levels, level_stride, d_betas, beta_stride, stream)
+
+
 # ---- four-to-one Ext FRI rounds under coset leaves (include/toyni_hip.h 3m) ----
 def fri_fold4_commit_ext_device(ctx, d_evals: int, d_out: int, m: int, beta4, x0: int, d_salts: int, d_levels: int, stream: int = 0) -> None:
     """One four-to-one round: the m / 4 folded Ext elements to d_out (two pairwise folds, beta4 on x0 then beta4^2 on x0^2, in one
