@@ -1016,6 +1016,68 @@ int toyni_fri_query_positions_batch_device(const uint32_t* d_indices, size_t ind
                                            size_t batch, uint32_t* d_out, size_t out_stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * 3s. The BATCH dimension for the first half of a Fibonacci proof: batch forms of every call of the chain of 3q that 3r left single
+ *     (salts, mask, quotient, derive_z, the out-of-domain values, absorb_field, the DEEP layer, the query rows, the round roots), and a
+ *     strided copy.  With 3r and the transforms' own `batch` argument, `batch` proofs of one trace length are one chain of as many
+ *     launches as one proof (csrc/host/fib_prover_batch.hpp is that caller).
+ *     THE SPECIFICATION is 3r's: every call writes, for proof b < batch, exactly the bytes the single call writes when given proof b's
+ *     pointers.  ADDRESSING, the transcript array, the sticky per-proof `status`, the conventions (asynchronous on `stream`, no callback,
+ *     no host read, no new environment variable) and the ORDER OF THE REFUSALS (null pointers; batch == 0 or > 65535: TOYNI_E_RANGE; the
+ *     single call's own, with its codes and in its order; strides below the extent or against the single call's alignment rule:
+ *     TOYNI_E_RANGE) are 3r's.  The context, shift, log_blowup, n, mults and offsets are shared by the batch.  What the single call
+ *     accepts as "nothing to do" enqueues nothing.
+ *     KEYS: a proof's ChaCha key is read from DEVICE memory -- d_keys is batch x 32 bytes, contiguous, 4-byte aligned (otherwise
+ *     TOYNI_E_RANGE, judged with the strides), the key of proof b at d_keys + 32 b: a kernel-argument block cannot hold 65 535 keys.
+ *     RECORDS: toyni_poly_eval_dz_batch_device keeps batch x nblocks x npoints partial sums and then `batch` records in the context's
+ *     per-stream buffer, toyni_fib_deep_dz_batch_device `batch` records; with batch == 1 both layouts are the single call's.  On a
+ *     context warmed by one call on this stream with at least this batch and these sizes each call is a linear chain of kernels and
+ *     can be captured into a HIP graph (caveat of section 4).
+ *     No existing entry point, kernel symbol, record layout or written byte changes.  The section is implemented in a translation unit
+ *     of its own, csrc/batch/toyni_hip_fib_batch.hip, linked into the same library (a static archive of toyni_hip.hip alone, INTEGRATION.md 1,
+ *     does not contain these ten calls).
+ *     WHAT REMAINS single: the four-to-one phase of 3m, grinding (3n) and the staged-AIR chain of 3o / 3p.
+ * ---------------------------------------------------------------------------------------------- */
+/* toyni_chacha20_fill_device per proof: out_stride in BYTES, >= bytes and a multiple of 16. */
+int toyni_chacha20_fill_batch_device(void* d_out, size_t out_stride, size_t bytes, const uint8_t* d_keys, uint64_t nonce, size_t batch, void* stream);
+/* toyni_mask_poly_device per proof: coeff_stride >= n + mask_degree words. */
+int toyni_mask_poly_batch_device(uint32_t* d_coeffs, size_t coeff_stride, size_t n, unsigned mask_degree, const uint8_t* d_keys, uint64_t nonce,
+                                 size_t batch, void* stream);
+/* toyni_fib_quotient_device per proof (d_c_evals may be NULL; its stride is then not looked at): every stride >= N words.  A proof
+ * whose three pointers are 16-byte aligned takes the 16-byte accesses, any other the single words; the bytes are the same. */
+int toyni_fib_quotient_batch_device(toyni_ntt_ctx* ctx, const uint32_t* d_trace_lde, size_t trace_stride, uint32_t* d_c_evals, size_t c_stride,
+                                    uint32_t* d_q_evals, size_t q_stride, unsigned log_blowup, uint32_t shift, size_t batch, void* stream);
+/* toyni_transcript_squeeze_point_device on every transcript: proof b's z at d_z + b * z_stride (z_stride >= 1).  One wave per proof. */
+int toyni_transcript_squeeze_point_batch_device(toyni_transcript* d_tr, size_t batch, unsigned log_N, uint32_t shift, uint32_t* d_z, size_t z_stride,
+                                                void* stream);
+/* toyni_poly_eval_dz_device per proof: coeff_stride >= ncoeffs, z_stride >= 1, out_stride >= npoints.  Three launches; ncoeffs == 0
+ * writes zeros (two launches). */
+int toyni_poly_eval_dz_batch_device(toyni_ntt_ctx* ctx, const uint32_t* d_coeffs, size_t coeff_stride, size_t ncoeffs, const uint32_t* d_z,
+                                    size_t z_stride, const uint32_t* mults, unsigned npoints, size_t batch, uint32_t* d_out, size_t out_stride,
+                                    void* stream);
+/* toyni_transcript_absorb_fields_device on every transcript: proof b's `count` words at d_words + b * word_stride (word_stride >= count). */
+int toyni_transcript_absorb_fields_batch_device(toyni_transcript* d_tr, size_t batch, const uint32_t* d_words, size_t word_stride, size_t count,
+                                                void* stream);
+/* toyni_fib_deep_dz_device per proof (d_check may be NULL; its stride is then not looked at): trace_stride, q_stride and out_stride
+ * >= N words, ood_stride >= 4, z_stride and check_stride >= 1.  Two launches. */
+int toyni_fib_deep_dz_batch_device(toyni_ntt_ctx* ctx, const uint32_t* d_trace_lde, size_t trace_stride, const uint32_t* d_q_evals, size_t q_stride,
+                                   uint32_t* d_out, size_t out_stride, unsigned log_blowup, uint32_t shift, const uint32_t* d_z, size_t z_stride,
+                                   const uint32_t* d_ood, size_t ood_stride, uint32_t trace_len, uint32_t* d_check, size_t check_stride, size_t batch,
+                                   void* stream);
+/* toyni_query_rows_device per proof: index_stride >= count, out_stride >= count x noffsets. */
+int toyni_query_rows_batch_device(const uint32_t* d_indices, size_t index_stride, size_t count, size_t n, const uint32_t* offsets, unsigned noffsets,
+                                  size_t batch, uint32_t* d_out, size_t out_stride, void* stream);
+/* toyni_fri_phase_roots_device per proof: level_stride in BYTES, a multiple of 16 and at least the trees' extent (32 bytes x the sum of
+ * 2 (m_first >> k) - 1 over the rounds); root_stride in bytes, >= 32 x rounds and a multiple of 4.  One launch, one block per proof. */
+int toyni_fri_phase_roots_batch_device(const uint8_t* d_levels, size_t level_stride, size_t m_first, unsigned rounds, size_t batch, uint8_t* d_roots,
+                                       size_t root_stride, void* stream);
+/* `rows` stream-ordered copies in ONE launch: row r copies row_bytes bytes from d_src + r * src_stride to d_dst + r * dst_stride (strides in
+ * bytes) -- what `rows` calls of toyni_memcpy_d2d_async would write.  It gathers roots that lie level_stride apart, copies final layers,
+ * and spreads n-word rows into wider coefficient slots.  16-byte accesses where both pointers and both strides are multiples of 16, words
+ * otherwise.  Overlapping ranges are the caller's contract.  rows == 0 or row_bytes == 0 enqueues nothing.  TOYNI_E_NULL for a null
+ * pointer; TOYNI_E_RANGE for rows > 65535, a pointer, stride or row_bytes that is no multiple of 4, or a stride below row_bytes. */
+int toyni_copy_rows_device(void* d_dst, size_t dst_stride, const void* d_src, size_t src_stride, size_t row_bytes, size_t rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:
  *     src/fibonacci.rs:133-150,186-198,222-245, src/math/polynomial.rs:134-144, src/merkle.rs:50-80).  All asynchronous on
  *     `stream`; packed u32 device data; ctx = a context of size N = the LDE size (its domain table supplies x_i = shift w_N^i).

@@ -190,6 +190,19 @@ SIGNATURES = {
                                                                    c_void_p, c_size, c_void_p, c_size, c_void_p, c_size, c_void_p]),
     "toyni_transcript_squeeze_indices_batch_device": (c_int, [c_void_p, c_size, c_size, c_u32, c_void_p, c_size, c_void_p]),
     "toyni_fri_query_positions_batch_device": (c_int, [c_void_p, c_size, c_size, c_size, c_size, c_size, c_void_p, c_size, c_void_p]),
+    # section 3s
+    "toyni_chacha20_fill_batch_device": (c_int, [c_void_p, c_size, c_size, c_void_p, c_u64, c_size, c_void_p]),
+    "toyni_mask_poly_batch_device": (c_int, [c_void_p, c_size, c_size, ctypes.c_uint, c_void_p, c_u64, c_size, c_void_p]),
+    "toyni_fib_quotient_batch_device": (c_int, [c_void_p, c_void_p, c_size, c_void_p, c_size, c_void_p, c_size, ctypes.c_uint, c_u32, c_size, c_void_p]),
+    "toyni_transcript_squeeze_point_batch_device": (c_int, [c_void_p, c_size, ctypes.c_uint, c_u32, c_void_p, c_size, c_void_p]),
+    "toyni_poly_eval_dz_batch_device": (c_int, [c_void_p, c_void_p, c_size, c_size, c_void_p, c_size, c_void_p, ctypes.c_uint, c_size, c_void_p, c_size,
+                                                c_void_p]),
+    "toyni_transcript_absorb_fields_batch_device": (c_int, [c_void_p, c_size, c_void_p, c_size, c_size, c_void_p]),
+    "toyni_fib_deep_dz_batch_device": (c_int, [c_void_p, c_void_p, c_size, c_void_p, c_size, c_void_p, c_size, ctypes.c_uint, c_u32, c_void_p, c_size,
+                                               c_void_p, c_size, c_u32, c_void_p, c_size, c_size, c_void_p]),
+    "toyni_query_rows_batch_device": (c_int, [c_void_p, c_size, c_size, c_size, c_void_p, ctypes.c_uint, c_size, c_void_p, c_size, c_void_p]),
+    "toyni_fri_phase_roots_batch_device": (c_int, [c_void_p, c_size, c_size, ctypes.c_uint, c_size, c_void_p, c_size, c_void_p]),
+    "toyni_copy_rows_device": (c_int, [c_void_p, c_size, c_void_p, c_size, c_size, c_size, c_void_p]),
     # section 3c
     "toyni_fri_fold_commit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -5374,6 +5374,26 @@ int toyni_fri_phase_roots_device(const uint8_t* d_levels, size_t m_first, unsign
     return (int)hipGetLastError();
 }
 
+// ---- section 3s lives in a translation unit of its own (toyni_hip_fib_batch.hip): what it needs of this one ----
+// Not part of the C ABI.  The other unit reads a context through these, and files its launches in this unit's registry.
+extern "C++" {   // (this part of the file is inside extern "C")
+namespace toyni_internal {
+int ctx_log_n(const toyni_ntt_ctx* c) { return c->plan.log_n; }
+DomainArgs ctx_domain_args(toyni_ntt_ctx* c, unsigned log_m, uint32_t shift) { return domain_args(c, log_m, shift); }
+bool note_launch(const void* kernel) { return launch_registry::note(kernel); }
+// enqueue(user, d_words) with the context locked and its device current; words > 0: d_words is the stream's buffer, grown to `words`
+int ctx_enqueue(toyni_ntt_ctx* c, void* stream, size_t words, int (*enqueue)(void* user, uint32_t* d_words), void* user) {
+    TOYNI_CTX_LOCK(c);
+    DeviceGuard guard(c->device);
+    if (words == 0) return enqueue(user, nullptr);
+    hipStream_t s = (hipStream_t)stream;
+    toyni_ntt_ctx::Scratch& sc = scratch_for(c, s);
+    if (int rc = grow(c, s, (void**)&sc.d_lde32, &sc.lde32_words, words, sizeof(uint32_t))) return rc;
+    return enqueue(user, sc.d_lde32);
+}
+}  // namespace toyni_internal
+}  // extern "C++"
+
 // ---- section 3g: accumulator columns ----
 size_t toyni_column_scan_tile(void) { return SCAN_TILE; }
 

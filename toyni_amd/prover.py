@@ -798,6 +798,16 @@ class DeviceTranscriptBatch:
         check(lib.toyni_transcript_squeeze_indices_batch_device(self.ptr, self.batch, count, mx, d_out, out_stride, stream or None),
               "GPU batched transcript index squeeze failed")
 
+    def squeeze_point(self, log_N: int, shift: int, d_z: int, z_stride: int = 1, stream: int = 0) -> None:
+        """derive_z per proof (include/toyni_hip.h 3s): proof b's z to d_z + b * z_stride words."""
+        check(lib.toyni_transcript_squeeze_point_batch_device(self.ptr, self.batch, log_N, shift, d_z, z_stride, stream or None),
+              "GPU batched transcript point squeeze failed")
+
+    def absorb_fields(self, d_words: int, word_stride: int, count: int, stream: int = 0) -> None:
+        """Transcript b absorbs the `count` field words at d_words + b * word_stride (absorb_field, 8 bytes each)."""
+        check(lib.toyni_transcript_absorb_fields_batch_device(self.ptr, self.batch, d_words or None, word_stride, count, stream or None),
+              "GPU batched transcript field absorb failed")
+
     def download(self):
         """[(state bytes, status)] per proof after a synchronous copy (synchronise the stream that carries the work first)."""
         host = np.zeros((self.batch, 1024), dtype=np.uint8)
@@ -827,6 +837,57 @@ def fri_query_positions_batch_device(d_indices: int, index_stride: int, count: i
                                      out_stride: int, stream: int = 0) -> None:
     check(lib.toyni_fri_query_positions_batch_device(d_indices, index_stride, count, m0, final_size, batch, d_out, out_stride, stream or None),
           "GPU batched query positions failed")
+
+
+# ---- the batch dimension of the first half of a Fibonacci proof (include/toyni_hip.h 3s): thin bindings, strides as the header counts them ----
+def chacha20_fill_batch_device(d_out: int, out_stride: int, nbytes: int, d_keys: int, nonce: int, batch: int, stream: int = 0) -> None:
+    """Per proof `nbytes` keystream bytes at d_out + b * out_stride under the key at d_keys + 32 b (device memory)."""
+    check(lib.toyni_chacha20_fill_batch_device(d_out or None, out_stride, nbytes, d_keys or None, nonce, batch, stream or None),
+          "GPU batched ChaCha20 fill failed")
+
+
+def mask_poly_batch_device(d_coeffs: int, coeff_stride: int, n: int, mask_degree: int, d_keys: int, nonce: int, batch: int, stream: int = 0) -> None:
+    check(lib.toyni_mask_poly_batch_device(d_coeffs or None, coeff_stride, n, mask_degree, d_keys or None, nonce, batch, stream or None),
+          "GPU batched mask failed")
+
+
+def fib_quotient_batch_device(ctx, d_trace_lde: int, trace_stride: int, d_c_evals: int, c_stride: int, d_q_evals: int, q_stride: int,
+                              log_blowup: int, shift: int, batch: int, stream: int = 0) -> None:
+    check(lib.toyni_fib_quotient_batch_device(ctx.handle, d_trace_lde or None, trace_stride, d_c_evals or None, c_stride, d_q_evals or None, q_stride,
+                                              log_blowup, shift, batch, stream or None), "GPU batched constraint / quotient evaluation failed")
+
+
+def poly_eval_dz_batch_device(ctx, d_coeffs: int, coeff_stride: int, ncoeffs: int, d_z: int, z_stride: int, mults, batch: int, d_out: int,
+                              out_stride: int, stream: int = 0) -> None:
+    m = np.ascontiguousarray(mults, dtype=np.uint32).ravel()
+    check(lib.toyni_poly_eval_dz_batch_device(ctx.handle, d_coeffs or None, coeff_stride, ncoeffs, d_z or None, z_stride, m.ctypes.data, m.size, batch,
+                                              d_out or None, out_stride, stream or None), "GPU batched polynomial evaluation (device point) failed")
+
+
+def fib_deep_dz_batch_device(ctx, d_trace_lde: int, trace_stride: int, d_q_evals: int, q_stride: int, d_out: int, out_stride: int, log_blowup: int,
+                             shift: int, d_z: int, z_stride: int, d_ood: int, ood_stride: int, trace_len: int, d_check: int, check_stride: int,
+                             batch: int, stream: int = 0) -> None:
+    check(lib.toyni_fib_deep_dz_batch_device(ctx.handle, d_trace_lde or None, trace_stride, d_q_evals or None, q_stride, d_out or None, out_stride,
+                                             log_blowup, shift, d_z or None, z_stride, d_ood or None, ood_stride, trace_len, d_check or None,
+                                             check_stride, batch, stream or None), "GPU batched DEEP evaluation (device point) failed")
+
+
+def query_rows_batch_device(d_indices: int, index_stride: int, count: int, n: int, offsets, batch: int, d_out: int, out_stride: int,
+                            stream: int = 0) -> None:
+    off = np.ascontiguousarray(offsets, dtype=np.uint32).ravel()
+    check(lib.toyni_query_rows_batch_device(d_indices or None, index_stride, count, n, off.ctypes.data, off.size, batch, d_out or None, out_stride,
+                                            stream or None), "GPU batched query rows failed")
+
+
+def fri_phase_roots_batch_device(d_levels: int, level_stride: int, m_first: int, rounds: int, batch: int, d_roots: int, root_stride: int,
+                                 stream: int = 0) -> None:
+    check(lib.toyni_fri_phase_roots_batch_device(d_levels or None, level_stride, m_first, rounds, batch, d_roots or None, root_stride, stream or None),
+          "GPU batched phase roots failed")
+
+
+def copy_rows_device(d_dst: int, dst_stride: int, d_src: int, src_stride: int, row_bytes: int, rows: int, stream: int = 0) -> None:
+    """`rows` stream-ordered copies of row_bytes bytes in one launch; strides in bytes."""
+    check(lib.toyni_copy_rows_device(d_dst or None, dst_stride, d_src or None, src_stride, row_bytes, rows, stream or None), "GPU row copy failed")
 
 
 def _phase_batch(entry, what, ctx, d_layer0, layer0_stride, m0, x0, final_size, d_salts, salt_stride, transcripts, d_layers, layers_stride,
