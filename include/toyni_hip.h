@@ -1078,6 +1078,114 @@ int toyni_fri_phase_roots_batch_device(const uint8_t* d_levels, size_t level_str
 int toyni_copy_rows_device(void* d_dst, size_t dst_stride, const void* d_src, size_t src_stride, size_t row_bytes, size_t rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * 3t. VERIFYING a batch of Fibonacci proofs of one trace length on the device: what StarkVerifier::verify does (src/verifier.rs:14-232),
+ *     one verdict word per proof, in FIVE launches whatever the batch, with no host in the loop: the caller uploads the images once,
+ *     downloads 4 x batch bytes once and synchronises once.  The chain is linear and can be captured into a HIP graph.
+ *     THE PROOF IMAGE.  A proof of trace length n is a fixed-size byte image; N = 32 n, C = next_pow2(n + 140), F = log2 C folds,
+ *     final_size = N / C <= 16, Q = 44.  In order:
+ *       roots            trace root, quotient root, fri_commitments[0 .. F]: (F + 3) x 32 bytes
+ *       OOD values       t_z, t_gz, t_ggz, q_z: 4 words
+ *       claimed indices  QueryProof::index of the Q queries: Q words
+ *       final layer      fri_final_layer: final_size words; then zero padding to a multiple of 8 bytes
+ *       opening records  back to back, each the record of toyni_merkle_open_device (3c), in the provers' order: 3 Q over the trace tree
+ *                        (N leaves; rows qi, qi + 32, qi + 64 mod N per query), Q over the quotient tree (N), 2 Q over layer 0 = the DEEP
+ *                        tree (N; qi and qi + N / 2), 2 Q over the tree of N >> k leaves for every layer k = 1 .. F - 1
+ *     -- the records are Proof::opening_records of csrc/host/fib_prover.hpp as they lie.  image_bytes is rounded up to a multiple of 16;
+ *     images lie image_stride bytes apart (a multiple of 16, >= image_bytes).  The image carries NO opening indices, no z and no transcript
+ *     state: the verifier derives them.  The reference's structural refusals (lde_size, fold_count, final_size, query_count,
+ *     fri_opening_count) cannot occur in an image of the right size; the packers (toyni_amd/verifier.py, csrc/host/fib_verifier.hpp)
+ *     refuse them on the host under those names.
+ *     THE VERDICT WORD.  0 = accept; otherwise (q + 1) << 8 | code, q the query (q + 1 = 0 for the checks made once per proof) and the
+ *     codes in the order in which the reference visits its checks, so that the word names exactly the check at which src/verifier.rs
+ *     returns false.  It is a function of the image alone, never of the grid or the schedule (no atomics: every query leaves the key of
+ *     its first failing check in the work buffer and the last kernel takes the minimum).  A proof that fails, fails alone.
+ *     STRICTER THAN THE REFERENCE in one point: a record counts only if its `depth` position bytes spell the index the VERIFIER derived
+ *     (byte l = bit l of the index, 1 = the sibling is the left input).  The reference trusts the prover's position flags for the FRI
+ *     openings (src/verifier.rs:176-205) and compares indices only for the trace rows.  An honest prover's records pass both.  Also: a
+ *     value word >= p or a non-zero upper value word -- nothing a BabyBear can hold -- is TOYNI_FIB_MALFORMED, and fails its record.
+ *     The section is a translation unit of its own, csrc/verify/toyni_hip_verify.hip, linked into the same library.
+ *     OUT OF SCOPE: verifying a batch prover's buffers where they lie, the Ext / staged-AIR proofs, four-to-one layers, grinding.
+ * ---------------------------------------------------------------------------------------------- */
+#define TOYNI_FIB_ACCEPT 0
+#define TOYNI_FIB_MALFORMED 1             /* a field word of the image is not canonical ("malformed") */
+#define TOYNI_FIB_OOD 2                   /* C(z) != Q(z) Z(z) ("ood") */
+#define TOYNI_FIB_FINAL_NOT_CONSTANT 3    /* "final_not_constant" */
+#define TOYNI_FIB_FINAL_COMMITMENT 4      /* the tree over the final layer does not have the last commitment as its root ("final_commitment") */
+#define TOYNI_FIB_QUERY_INDEX 5           /* a claimed index differs from the derived one ("query_index") */
+#define TOYNI_FIB_TRACE_MERKLE 6          /* "trace_merkle" */
+#define TOYNI_FIB_QUOTIENT_MERKLE 7       /* "quotient_merkle" */
+#define TOYNI_FIB_DEEP_MERKLE 8           /* "deep_merkle" */
+#define TOYNI_FIB_DEEP_VALUE 9            /* "deep_value" */
+#define TOYNI_FIB_FRI_MERKLE(k) (16 + 2 * ((k) - 1))        /* layer k = 1 .. F - 1 ("fri_merkle") */
+#define TOYNI_FIB_FRI_CONSISTENCY(k) (17 + 2 * ((k) - 1))   /* "fri_consistency" */
+#define TOYNI_FIB_FINAL_VALUE 255         /* the fold chain does not land on fri_final_layer[pos] ("final_value") */
+#define TOYNI_FIB_MAX_GROUPS 32
+typedef struct {
+    size_t trace_len, lde_size, folds, final_size, queries;
+    size_t roots_offset, nroots;                       /* byte offsets into an image from here on */
+    size_t ood_offset, indices_offset, final_offset, records_offset;
+    size_t ngroups;                                    /* folds + 2: trace, quotient, layer 0 (DEEP), layers 1 .. folds - 1 */
+    size_t group_offset[TOYNI_FIB_MAX_GROUPS];         /* first record of the group */
+    size_t group_leaves[TOYNI_FIB_MAX_GROUPS];
+    size_t group_records[TOYNI_FIB_MAX_GROUPS];
+    size_t group_record_bytes[TOYNI_FIB_MAX_GROUPS];   /* toyni_merkle_open_record_bytes(group_leaves) */
+    size_t nrecords, image_bytes;
+} toyni_fib_proof_layout;
+/* Host only.  TOYNI_E_NULL; TOYNI_E_INVALID_SIZE unless trace_len is a power of two in [8, 2^22] (toyni_fib_proof_image_bytes: 0). */
+int toyni_fib_proof_layout_of(size_t trace_len, toyni_fib_proof_layout* layout);
+size_t toyni_fib_proof_image_bytes(size_t trace_len);
+/* The name of the check a verdict word stands for, as tests/harness/fib_verifier.py puts it into `why` ("accept" for 0, "unknown"). */
+const char* toyni_fib_verdict_string(uint32_t word);
+
+/* The general call any AIR verifier needs: records of several trees of `batch` proofs checked in ONE launch (one per 32 groups with
+ * records).  Record r of proof b of a group lies at d_records + b * record_stride + r * toyni_merkle_open_record_bytes(leaves), the
+ * index it must open at d_indices[b * index_stride + r] (device data), its root at d_root + b * root_stride, and
+ * d_flags[b * flag_stride + r] receives 1 if the record's leaf and path hash to the root AND its position bytes spell that index AND its
+ * value is canonical, else 0 (byte l = bit l of the index -- or 1 where an odd level pairs its last node with itself, as MerkleTree::get_proof
+ * writes it; leaves need not be a power of two).  Nothing read from a record or from d_indices is used as an address.  A group with nrecords == 0 is skipped.
+ * TOYNI_E_NULL for a null pointer; TOYNI_E_RANGE for batch == 0 or > 65535, leaves == 0 or > 2^32, nrecords > 2^32 / 64, d_records or
+ * record_stride no multiple of 8, another pointer no multiple of 4, root_stride no multiple of 4, or a stride below its extent
+ * (nrecords records; nrecords words; 32 bytes).
+ * The call takes no context: it launches on the CURRENT device, which the caller has made the device of these pointers (toyni_set_device);
+ * the composite call below names its device through its context. */
+typedef struct {
+    const uint8_t* d_records;
+    size_t record_stride;     /* bytes */
+    size_t nrecords, leaves;
+    int salted;               /* the leaf is SHA256(00 || salt || value) -- or SHA256(00 || value), the record's salt bytes ignored */
+    const uint32_t* d_indices;
+    size_t index_stride;      /* words */
+    const uint8_t* d_root;
+    size_t root_stride;       /* bytes */
+    uint32_t* d_flags;
+    size_t flag_stride;       /* words */
+} toyni_merkle_verify_group;
+int toyni_merkle_verify_records_batch_device(const toyni_merkle_verify_group* groups, size_t ngroups, size_t batch, void* stream);
+
+/* Verifies the `batch` images at d_images + b * image_stride and writes d_verdicts[b].  ctx: a context of size N = 32 trace_len (it names
+ * the device; nothing of it is written).  d_work: toyni_fib_verify_work_bytes(trace_len, batch) bytes, 16-byte aligned, scratch of the
+ * call; nothing of its earlier contents is read.  Defined after the call, per proof: the transcript's length, status and its `len` state
+ * bytes (initialised on the device to "toyni-stark-v1"), z, the key of the global checks, the F betas, the 44 derived indices, the keys of
+ * the 44 queries, the expected index and the word of every record.  The rest -- two spare words, the unused betas, the state bytes beyond
+ * `len`, the padding up to the proof's stride -- is never written.  Five launches:
+ *   fib_verify_replay_kernel        one wave per proof (one lane active): absorb both roots, derive_z, absorb the four values and
+ *                                   fri_commitments[0], squeeze beta_(k-1) and absorb root k for k = 1 .. F, squeeze_indices(44, N / 2)
+ *   fib_verify_global_kernel        one wave per proof, 516 bytes of LDS (16 digests and one word): every field word canonical, C(z) =
+ *                                   Q(z) Z(z), the final layer constant, its unsalted tree's root the last commitment; the positions
+ *                                   every record must open, from the DERIVED indices
+ *   merkle_verify_records_batch_kernel   the call above over all F + 2 groups, the proof index fastest
+ *   fib_verify_query_kernel         one thread per (proof, query): claimed index, record words, the DEEP value rebuilt over
+ *                                   (x_i - z)^-1, the fold chain with x = (7 w_N^lo)^(2^k) and one inversion per layer, the final value
+ *   fib_verify_verdict_kernel       one wave per proof (one lane active): the minimum key
+ * REFUSALS, before anything is enqueued and with the outputs untouched, in this order: TOYNI_E_NULL for a null pointer; TOYNI_E_RANGE for
+ * batch == 0 or > 65535; TOYNI_E_INVALID_SIZE unless trace_len is a power of two in [8, 2^22]; TOYNI_E_RANGE unless the context's n is
+ * 32 trace_len; TOYNI_E_RANGE for d_images or d_work not 16-byte aligned, d_verdicts not 4-byte aligned, image_stride below
+ * toyni_fib_proof_image_bytes(trace_len) or no multiple of 16. */
+size_t toyni_fib_verify_work_bytes(size_t trace_len, size_t batch);
+int toyni_fib_verify_batch_device(toyni_ntt_ctx* ctx, const uint8_t* d_images, size_t image_stride, size_t trace_len, size_t batch, void* d_work,
+                                  uint32_t* d_verdicts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * 3c. One FRI round, and the pointwise steps of the Fibonacci prover on the LDE coset (oracle:
  *     src/fibonacci.rs:133-150,186-198,222-245, src/math/polynomial.rs:134-144, src/merkle.rs:50-80).  All asynchronous on
  *     `stream`; packed u32 device data; ctx = a context of size N = the LDE size (its domain table supplies x_i = shift w_N^i).

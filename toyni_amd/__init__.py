@@ -21,5 +21,7 @@ from . import prover  # noqa: F401
 from .prover import AirBuilder, AirProgram, air_insns, air_quotient_device  # noqa: F401  (include/toyni_hip.h 3f)
 from .prover import air_ext_weights, air_quotient_ext_device  # noqa: F401  (include/toyni_hip.h 3k)
 from .prover import pow_check  # noqa: F401  (include/toyni_hip.h 3n)
+from . import verifier  # noqa: F401
+from .verifier import pack_fib_proof, verify_fib_batch  # noqa: F401  (include/toyni_hip.h 3t)
 
 P = 2013265921

@@ -203,6 +203,13 @@ SIGNATURES = {
     "toyni_query_rows_batch_device": (c_int, [c_void_p, c_size, c_size, c_size, c_void_p, ctypes.c_uint, c_size, c_void_p, c_size, c_void_p]),
     "toyni_fri_phase_roots_batch_device": (c_int, [c_void_p, c_size, c_size, ctypes.c_uint, c_size, c_void_p, c_size, c_void_p]),
     "toyni_copy_rows_device": (c_int, [c_void_p, c_size, c_void_p, c_size, c_size, c_size, c_void_p]),
+    # section 3t
+    "toyni_fib_proof_layout_of": (c_int, [c_size, c_void_p]),
+    "toyni_fib_proof_image_bytes": (c_size, [c_size]),
+    "toyni_fib_verdict_string": (ctypes.c_char_p, [c_u32]),
+    "toyni_merkle_verify_records_batch_device": (c_int, [c_void_p, c_size, c_size, c_void_p]),
+    "toyni_fib_verify_work_bytes": (c_size, [c_size, c_size]),
+    "toyni_fib_verify_batch_device": (c_int, [c_void_p, c_void_p, c_size, c_size, c_size, c_void_p, c_void_p, c_void_p]),
     # section 3c
     "toyni_fri_fold_commit_device": (c_int, [c_void_p, c_void_p, c_void_p, c_size, c_u32, c_u32, c_void_p, c_void_p, c_void_p]),
     "toyni_fri_commit_phase_device": (c_int, [c_void_p, c_void_p, c_size, c_u32, c_size, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
